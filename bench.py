@@ -2,6 +2,7 @@
 """bench.py -- h-Edit sampling loop on MI355X (BASELINE.json metric: edited images/s).
 
     python bench.py --gpus 1 --steps K --warmup W            # one process
+    python bench.py ... --dump-outputs DIR                    # + the last timed step's outputs as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one pass of the hot path over one batch of synthetic input: the complete reverse-time
@@ -73,10 +74,32 @@ def parse():
     ap.add_argument("--reuse-orig-eps", action="store_true",
                     help="opt-in: reuse eps(x_orig, t-1, {null,src}) of the P2P pass in the next base pass "
                          "(7 instead of 9 sample-forwards per step; NOT the reference's evaluation count)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32, "
+                         "at most 64 MB in all; a larger output is replaced by a fixed seeded sample of its elements).  The inputs "
+                         "are seeded, so two builds run with the same arguments can be compared output for output")
     return ap.parse_args()
 
 
-def face_pass(args, rank, dev, dist, n, T, K, steps, warmup):
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, rank=0, world=1):
+    """--dump-outputs: arrays {name: tensor} -> path/<name>.npy in float32 (rank r > 0: <name>_rank<r>.npy).  An array over its
+    share of the budget is written as a flat sample of its elements: the same seeded element indices on every run with the
+    same arguments, in ascending order."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // (len(arrays) * world)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, (name if rank == 0 else f"{name}_rank{rank}") + ".npy"), a)
+
+
+def face_pass(args, rank, dev, dist, n, T, K, steps, warmup, dump=None):
     """BASELINE configs[3] per GPU: face-swapping h-Edit-R (face-swapping/inversion/h_edit_R.py) -- pixel DDPM UNet
     (HIP, CelebA-HQ 256 shape, random init) guided by the ArcFace identity reward (IR-SE50) and the LPIPS-VGG
     perceptual reward, both native executors (loss + image gradient in one call each), T steps, K implicit steps:
@@ -122,6 +145,8 @@ def face_pass(args, rank, dev, dist, n, T, K, steps, warmup):
         from hedit import dist as HD
         elapsed = HD.max_over_ranks(elapsed, device=dev)
         world = dist.get_world_size()
+    if dump:
+        dump_outputs(dump, {"swapped": out}, rank, world)
     # the eps-network alone, same batch, HIP events on the launch stream
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ev0.record()
@@ -157,7 +182,7 @@ def run_face(args, world, rank, local, dev, dist):
     n = args.images if args.images != 24 else 32
     T = args.diffusion_steps if args.diffusion_steps != 50 else 100
     K = args.opt_steps if args.opt_steps != 1 else 3
-    out_json = face_pass(args, rank, dev, dist, n, T, K, args.steps, args.warmup)
+    out_json = face_pass(args, rank, dev, dist, n, T, K, args.steps, args.warmup, dump=args.dump_outputs)
     if rank == 0:
         print(json.dumps(out_json))
     if dist is not None:
@@ -337,6 +362,8 @@ def main():
         elapsed = HD.max_over_ranks(elapsed, device=dev)
     calls["prof"] = False
     unet_calls = calls["n"]
+    if args.dump_outputs:       # before the auxiliary blocks below run the engine again
+        dump_outputs(args.dump_outputs, {"edit": edit, "recon": recon}, rank, world)
 
     # auxiliary (outside the timed region): BASELINE configs[1] read literally = ONE image; latency
     single_s = None

@@ -45,6 +45,24 @@ def test_bench_line_contract(extra):
     assert d["recon_rel_err"] < 2e-6
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the (edit, recon) latents the timed path returned in its last step, as float32 .npy files; the inputs
+    are seeded, so a second run with the same arguments writes the same arrays"""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = _run(["--dump-outputs", str(tmp_path / f"run{i}"), "--no-config2", "--no-single"])
+        assert d["steps"] == 1 and d["ms_per_step"] > 0
+        arrs = {name: np.load(tmp_path / f"run{i}" / f"{name}.npy") for name in ("edit", "recon")}
+        assert sorted(os.listdir(tmp_path / f"run{i}")) == ["edit.npy", "recon.npy"]
+        for a in arrs.values():
+            assert a.dtype == np.float32 and a.shape == (3, 4, 32, 32) and np.isfinite(a).all()
+        dumps.append(arrs)
+    for name in ("edit", "recon"):
+        a, b = dumps[0][name], dumps[1][name]
+        assert np.linalg.norm(a - b) <= 1e-5 * np.linalg.norm(a), name
+
+
 def _free_port():
     import socket
     s = socket.socket()
