@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """bench.py -- h-Edit sampling loop on MI355X (BASELINE.json metric: edited images/s).
 
-    python bench.py --gpus 1 --steps K --warmup W            # one process
+    python bench.py --gpus 1 --steps K --warmup W            # one process: set-up, W warm-up steps, K timed steps, the line
     python bench.py ... --dump-outputs DIR                    # + the last timed step's outputs as DIR/<name>.npy
+    python bench.py ... --full                                # + the auxiliary blocks (see below)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" = one pass of the hot path over one batch of synthetic input: the complete reverse-time
@@ -14,6 +15,11 @@ lock-step: 50 x (1 base pass of 4n rows + 1 source pass of n rows + 1 P2P pass o
 rows ride along in the P2P pass as un-edited rows; --no-fuse-src issues them as their own call).  Inputs (weights,
 inverted latents x_T, noise maps z_t, text embeddings) are resident in HBM before the timed
 region; DDPM inversion is outside it (it is the step BEFORE the path).
+
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs, the line.  Everything
+that takes runs of its own after the timed region is behind --full: the one-image latency, the reuse_orig_eps pass, BASELINE
+configs[2] / [3] / [4], the half-storage child, the CPU baseline, and for --workload face the eps-network timing.  Their
+--no-* flags still drop single blocks from a --full run; in a plain run those blocks are null.
 
 Multi-GPU: one process per GPU, images sharded across ranks (weak scaling, no data-path
 collective); rank 0 creates the weights and broadcasts them over RCCL/xGMI once at start-up.
@@ -59,17 +65,20 @@ def parse():
                     help="16-bit storage format of activations / weights: bf16 = BASELINE configs[1] and the default line; f16 = the "
                          "half-storage build of the same kernels (libhedit_hip_f16.so, eps error 1.5e-3 instead of 1.2e-2 vs fp32). "
                          "Default: the HEDIT_STORAGE environment variable, else bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the auxiliary blocks (one-image latency, reuse_orig_eps pass, configs[2] / [3] "
+                         "/ [4], half storage, CPU baseline, face eps-network timing); a plain run leaves them null")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--prof-every", type=int, default=25, help="bracket every n-th UNet call with HIP events")
     ap.add_argument("--tiny", action="store_true", help="debug: tiny network instead of SD-1.5 shape")
     ap.add_argument("--no-fuse-src", action="store_true",
                     help="issue the source-prompt pass as its own UNet call like the reference instead of "
                          "as n extra rows of the P2P pass (same arithmetic either way)")
     ap.add_argument("--force-dist", action="store_true", help="init the RCCL process group even for one rank")
-    ap.add_argument("--no-single", action="store_true", help="skip the auxiliary one-image latency measurement")
-    ap.add_argument("--no-half-storage", action="store_true", help="skip the auxiliary half-storage re-run of the loop (a child process)")
+    ap.add_argument("--no-single", action="store_true", help="with --full: skip the auxiliary one-image latency measurement")
+    ap.add_argument("--no-half-storage", action="store_true", help="with --full: skip the auxiliary half-storage re-run of the loop (a child process)")
     ap.add_argument("--no-config2", action="store_true",
-                    help="skip the auxiliary blocks after the timed region: BASELINE configs[2] (32 images, K = 3), configs[3] (face "
+                    help="with --full: skip the auxiliary blocks after the timed region: BASELINE configs[2] (32 images, K = 3), configs[3] (face "
                          "swapping, 32 and 8 faces), configs[4] (text + style, 16 images), one pass each")
     ap.add_argument("--reuse-orig-eps", action="store_true",
                     help="opt-in: reuse eps(x_orig, t-1, {null,src}) of the P2P pass in the next base pass "
@@ -99,12 +108,13 @@ def dump_outputs(path, arrays, rank=0, world=1):
         np.save(os.path.join(path, (name if rank == 0 else f"{name}_rank{rank}") + ".npy"), a)
 
 
-def face_pass(args, rank, dev, dist, n, T, K, steps, warmup, dump=None):
+def face_pass(args, rank, dev, dist, n, T, K, steps, warmup, dump=None, eps_timing=True):
     """BASELINE configs[3] per GPU: face-swapping h-Edit-R (face-swapping/inversion/h_edit_R.py) -- pixel DDPM UNet
     (HIP, CelebA-HQ 256 shape, random init) guided by the ArcFace identity reward (IR-SE50) and the LPIPS-VGG
     perceptual reward, both native executors (loss + image gradient in one call each), T steps, K implicit steps:
     T + 2 K (T - 1) eps evaluations per image (694 at T = 100, K = 3) and as many reward evaluations; n faces in
-    lock-step per GPU, one reference face and one source image per face.  -> the block of the JSON line."""
+    lock-step per GPU, one reference face and one source image per face.  -> the block of the JSON line.  eps_timing: time
+    the eps-network alone after the timed steps (its own 10 calls; the figures that need it are null without)."""
     import numpy as np
     from hedit.arcface import IDLoss
     from hedit.arcface.lpips_loss import LPIPS_Loss
@@ -148,17 +158,19 @@ def face_pass(args, rank, dev, dist, n, T, K, steps, warmup, dump=None):
     if dump:
         dump_outputs(dump, {"swapped": out}, rank, world)
     # the eps-network alone, same batch, HIP events on the launch stream
-    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    ev0.record()
-    for _ in range(10):
-        model(xT, 501.0)
-    ev1.record()
-    torch.cuda.synchronize()
-    unet_ms = ev0.elapsed_time(ev1) / 10
+    unet_ms = None
+    if eps_timing:
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record()
+        for _ in range(10):
+            model(xT, 501.0)
+        ev1.record()
+        torch.cuda.synchronize()
+        unet_ms = ev0.elapsed_time(ev1) / 10
     evals = T + 2 * K * (T - 1)
     flop_fwd = 0.497e12 if not args.tiny else 0.0
     imgs = steps * n * world
-    ach = flop_fwd * n / (unet_ms * 1e-3) / 1e12 if unet_ms > 0 else None
+    ach = flop_fwd * n / (unet_ms * 1e-3) / 1e12 if unet_ms else None
     return {
         "metric": "face-swapped images/sec (256^2, 100 steps, K=3)", "value": round(imgs / elapsed, 4), "unit": "images/s",
         "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": round(1e3 * elapsed / steps, 2),
@@ -168,8 +180,8 @@ def face_pass(args, rank, dev, dist, n, T, K, steps, warmup, dump=None):
                                f"K={K}; {n} faces per GPU in lock-step",
                    "images_per_gpu": n, "eps_evaluations_per_image": evals, "parallelism": f"replica-dp{world}"},
         "achieved_tflops_per_s_per_gpu": round(imgs * evals * flop_fwd / elapsed / 1e12 / world, 1),
-        "ms_per_eps_evaluation_batch": round(unet_ms, 3),
-        "unet_share_of_step": round(evals * unet_ms * 1e-3 / (elapsed / steps), 4),
+        "ms_per_eps_evaluation_batch": None if unet_ms is None else round(unet_ms, 3),
+        "unet_share_of_step": None if unet_ms is None else round(evals * unet_ms * 1e-3 / (elapsed / steps), 4),
         "roofline": {"bound": "mfma", "kernel": "hedit_ddpm_forward (all kernels of one eps evaluation)", "achieved": None if ach is None else round(ach, 1),
                      "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": None if ach is None else round(ach / MFMA_PEAK_TFLOPS, 4),
                      "traffic": None},
@@ -182,7 +194,7 @@ def run_face(args, world, rank, local, dev, dist):
     n = args.images if args.images != 24 else 32
     T = args.diffusion_steps if args.diffusion_steps != 50 else 100
     K = args.opt_steps if args.opt_steps != 1 else 3
-    out_json = face_pass(args, rank, dev, dist, n, T, K, args.steps, args.warmup, dump=args.dump_outputs)
+    out_json = face_pass(args, rank, dev, dist, n, T, K, args.steps, args.warmup, dump=args.dump_outputs, eps_timing=args.full)
     if rank == 0:
         print(json.dumps(out_json))
     if dist is not None:
@@ -367,7 +379,7 @@ def main():
 
     # auxiliary (outside the timed region): BASELINE configs[1] read literally = ONE image; latency
     single_s = None
-    if not args.no_single and style is None:
+    if args.full and not args.no_single and style is None:
         one_image()
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -380,7 +392,7 @@ def main():
     # :644-652); the kernels are batch-invariant, so reusing them gives the SAME BITS with 7 instead of 9 sample-forwards
     # per step.  Reported beside the headline, never as the headline (it is not the reference's evaluation count).
     cse = None
-    if not args.no_config2 and style is None and not args.reuse_orig_eps and world == 1:
+    if args.full and not args.no_config2 and style is None and not args.reuse_orig_eps and world == 1:
         torch.cuda.synchronize()
         t3 = time.perf_counter()
         e3, r3 = one_step(reuse=True)
@@ -394,7 +406,7 @@ def main():
     # auxiliary (outside the timed region): BASELINE configs[2] = 32 images in lock-step, 50 steps x K = 3
     # (text-guided/main_p2p.py:65 optimization_steps 3: (4 + 5*3) * 50 = 950 sample-forwards per image), ONE pass
     config2 = None
-    if not args.no_config2 and style is None and not args.tiny and K == 1 and world == 1:
+    if args.full and not args.no_config2 and style is None and not args.tiny and K == 1 and world == 1:
         n2, K2 = 32, 3
         step2, _, w02, t_inv2 = build_workload(n2, K2, seed_off=1000)
         torch.cuda.synchronize()
@@ -416,7 +428,7 @@ def main():
     # auxiliary (outside the timed region): BASELINE configs[4] per GPU = text + CLIP-style editing, 16 images in
     # lock-step, 50 steps, K = 1: every inner step adds the decoder forward + backward and the style encoder; ONE pass
     config4 = None
-    if not args.no_config2 and style is None and K == 1 and world == 1:
+    if args.full and not args.no_config2 and style is None and K == 1 and world == 1:
         n4 = 16 if not args.tiny else 2
         step4, _, w04, t_inv4 = build_workload(n4, 1, seed_off=2000, style=make_style())
         if args.tiny:
@@ -442,7 +454,7 @@ def main():
 
     # auxiliary (outside the timed region): BASELINE configs[3] per GPU = face swapping, 32 faces in lock-step, ONE pass
     config3 = None
-    if not args.no_config2 and style is None and K == 1 and world == 1:
+    if args.full and not args.no_config2 and style is None and K == 1 and world == 1:
         torch.cuda.empty_cache()
         blk = face_pass(args, rank, dev, None, 32 if not args.tiny else 2, 100 if not args.tiny else 6, 3, 1, 0)
         config3 = {k: blk[k] for k in ("value", "unit", "ms_per_step", "achieved_tflops_per_s_per_gpu", "ms_per_eps_evaluation_batch",
@@ -516,11 +528,11 @@ def main():
             roof["traffic_source"] = f"profiles/pmc_summary.json unreadable: {e}"
 
     cpu = None
-    if world == 1 and not args.no_cpu_baseline and not args.tiny and style is None:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.tiny and style is None:
         cpu = cpu_baseline(cfg, sd_cpu, T, K, tok)
     # auxiliary (after the timed region, rank 0, one GPU): the same loop in half storage, see half_storage_block.  Never part of `value`.
     half = None
-    if not args.no_config2 and not args.no_half_storage and style is None and world == 1 and not args.tiny and args.storage == "bf16":
+    if args.full and not args.no_config2 and not args.no_half_storage and style is None and world == 1 and not args.tiny and args.storage == "bf16":
         half = half_storage_block(args, imgs / elapsed)
 
     out = {
@@ -569,9 +581,9 @@ def half_storage_block(args, bf16_value):
                        "profiles/r05_f16_storage.txt; 50-step loop vs the oracle trajectory in both formats: profiles/r06_loop_divergence.txt; "
                        "both asserted by tests/test_gpu_unet.py / tests/test_gpu_loop_trajectory.py through tests/test_gpu_f16_suite.py"}
     try:
+        # a plain run (no --full): the timed loop and its line, none of the auxiliary blocks
         cmd = [sys.executable, os.path.abspath(__file__), "--storage", "f16", "--steps", "1", "--warmup", "1", "--images", str(args.images),
-               "--diffusion-steps", str(args.diffusion_steps), "--opt-steps", str(args.opt_steps), "--no-config2", "--no-cpu-baseline",
-               "--no-single", "--no-half-storage"]
+               "--diffusion-steps", str(args.diffusion_steps), "--opt-steps", str(args.opt_steps)]
         env = dict(os.environ)
         env.pop("HEDIT_STORAGE", None)
         r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)

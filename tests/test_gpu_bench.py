@@ -45,6 +45,23 @@ def test_bench_line_contract(extra):
     assert d["recon_rel_err"] < 2e-6
 
 
+def test_bench_full_adds_the_auxiliary_blocks():
+    """a plain run stops after the timed steps and leaves the auxiliary blocks null; --full runs them after the same timed steps
+    (at toy size: the one-image latency, the reuse_orig_eps pass, configs[3] and configs[4]; configs[2], the half-storage child
+    and the CPU baseline skip --tiny)"""
+    aux = ("single_image", "cse_variant", "configs2", "configs3", "configs4", "half_storage", "cpu_baseline")
+    plain = _run([])
+    assert all(plain[k] is None for k in aux), {k: plain[k] for k in aux}
+    full = _run(["--full"])
+    for k in ("metric", "unit", "higher_is_better", "dtype", "steps", "warmup"):
+        assert full[k] == plain[k], k
+    assert full["value"] > 0 and full["finite"] is True and full["recon_rel_err"] < 2e-6
+    assert full["single_image"]["latency_s"] > 0
+    assert full["cse_variant"]["value"] > 0
+    assert full["configs3"]["value"] > 0 and full["configs3"]["finite"] is True and full["configs3"]["ms_per_eps_evaluation_batch"] > 0
+    assert full["configs4"]["value"] > 0 and full["configs4"]["finite"] is True
+
+
 def test_bench_dump_outputs(tmp_path):
     """--dump-outputs DIR: the (edit, recon) latents the timed path returned in its last step, as float32 .npy files; the inputs
     are seeded, so a second run with the same arguments writes the same arrays"""

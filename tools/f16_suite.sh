@@ -21,5 +21,5 @@ timeout 300 python tests/diag/diag_storage_eps_error.py 2 2>&1 | grep storage | 
 # the 50-step loop against the committed oracle trajectory, both formats (seconds each: the oracle side is a fixture)
 (env HEDIT_STORAGE=bf16 timeout 300 python tests/diag/diag_loop_divergence.py; timeout 300 python tests/diag/diag_loop_divergence.py) 2>&1 | grep -v amdgpu.ids > "$out/loop_divergence.txt"
 grep "final" "$out/loop_divergence.txt" | tee -a "$out/summary.txt"
-timeout 1200 python bench.py --storage f16 --steps 1 --warmup 1 --no-config2 --no-cpu-baseline > "$out/bench_f16.json" 2> "$out/bench_f16.err"
+timeout 1200 python bench.py --full --storage f16 --steps 1 --warmup 1 --no-config2 --no-cpu-baseline > "$out/bench_f16.json" 2> "$out/bench_f16.err"
 tail -c 600 "$out/bench_f16.json" | tee -a "$out/summary.txt"

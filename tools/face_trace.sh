@@ -6,7 +6,7 @@ O=$R/gpurun_out/${ROUND_TAG:-r04}
 N=${1:-32}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/p_face -o trace -- python $R/bench.py --workload face --images $N --steps 1 --warmup 1 --diffusion-steps 20 > $O/bench_face_n${N}_under_rocprof.json 2> $O/rocprof_face.err
+timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/p_face -o trace -- python $R/bench.py --full --workload face --images $N --steps 1 --warmup 1 --diffusion-steps 20 > $O/bench_face_n${N}_under_rocprof.json 2> $O/rocprof_face.err
 db=$(find /tmp/p_face -name "*.db" | head -1)
 if [ -n "$db" ]; then
   python $R/tools/rocpd_stats.py $db --loop > $O/face_n${N}_kernel_stats.txt

@@ -6,7 +6,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r05
 mkdir -p $O
-cd $R && python bench.py > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.json; echo
+cd $R && python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 400 $O/bench.json; echo
 cd /tmp && export TMPDIR=/tmp
 timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/p_main -o trace -- python $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-single --no-config2 > $O/bench_under_rocprof.json 2> $O/rocprof.err
 db=$(find /tmp/p_main -name "*.db" | head -1)
@@ -14,7 +14,7 @@ db=$(find /tmp/p_main -name "*.db" | head -1)
 rm -rf /tmp/p_main
 [ "$1" == "quick" ] && exit 0
 bash $R/tools/pmc_traffic.sh > $O/pmc_traffic.log 2>&1; tail -8 $O/pmc_traffic.log
-timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/p_face -o trace -- python $R/bench.py --workload face --steps 1 --warmup 0 --diffusion-steps 20 > $O/bench_face_under_rocprof.json 2> $O/rocprof_face.err
+timeout 900 rocprofv3 --kernel-trace --stats -d /tmp/p_face -o trace -- python $R/bench.py --full --workload face --steps 1 --warmup 0 --diffusion-steps 20 > $O/bench_face_under_rocprof.json 2> $O/rocprof_face.err
 db=$(find /tmp/p_face -name "*.db" | head -1)
 [ -n "$db" ] && python $R/tools/rocpd_stats.py $db --loop > $O/face_kernel_stats.txt && head -10 $O/face_kernel_stats.txt
 [ -n "$db" ] && python $R/tools/rocpd_stats.py $db --loop --gaps > $O/face_gaps.txt && head -3 $O/face_gaps.txt

@@ -8,6 +8,6 @@ cp $R/gpurun_out/pmc_summary.json $R/profiles/pmc_summary.json
 cp $R/gpurun_out/pmc_summary.json $out/pmc_summary.json
 cd $R
 start=$(date +%s)
-python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "default bench rc=$? in $(( $(date +%s) - start )) s"
+python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "default bench rc=$? in $(( $(date +%s) - start )) s"
 tail -1 $out/bench_default.json | cut -c1-200
 bash tools/r06_trace.sh r06f | tail -2

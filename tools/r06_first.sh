@@ -10,7 +10,7 @@ for r in 120 40 5; do
   timeout 200 python tools/unet_time.py $r 5 2>&1 | grep storage | tee -a "$out/unet_ab.txt"
 done
 timeout 900 python -m pytest tests/test_gpu_ring_hazard.py tests/test_gpu_kernels.py tests/test_gpu_unet.py -q -x --tb=short -p no:cacheprovider > "$out/pytest_first.log" 2>&1; echo "pytest rc=$?"; tail -3 "$out/pytest_first.log"
-timeout 900 python bench.py --steps 2 --warmup 1 --no-config2 --no-half-storage --no-cpu-baseline > "$out/bench_first.json" 2> "$out/bench_first.err"; echo "bench rc=$?"
+timeout 900 python bench.py --full --steps 2 --warmup 1 --no-config2 --no-half-storage --no-cpu-baseline > "$out/bench_first.json" 2> "$out/bench_first.err"; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r06/bench_first.json").read().strip().splitlines()[-1])

@@ -12,7 +12,7 @@ for r in 120 96 40; do
   HEDIT_TEST_FLAGS=8 timeout 200 python tools/unet_time.py $r 5 2>&1 | grep storage | tee -a "$out/unet_ab2.txt"
   timeout 200 python tools/unet_time.py $r 5 2>&1 | grep storage | tee -a "$out/unet_ab2.txt"
 done
-timeout 900 python bench.py --steps 2 --warmup 1 --no-config2 --no-half-storage --no-cpu-baseline > "$out/bench_pconv.json" 2> "$out/bench_pconv.err"; echo "bench rc=$?"
+timeout 900 python bench.py --full --steps 2 --warmup 1 --no-config2 --no-half-storage --no-cpu-baseline > "$out/bench_pconv.json" 2> "$out/bench_pconv.err"; echo "bench rc=$?"
 python - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r06/bench_pconv.json").read().strip().splitlines()[-1])
