@@ -53,6 +53,7 @@ __global__ __launch_bounds__(256) void split3_kernel(Split3Params s, long total)
         switch (s.op) {
           case P_COPY: v = x; break;
           case P_AFFINE: v = s.p[pi] * x + s.q[pi]; break;
+          case P_AFFINE_RELU: { const float t = s.p[pi] * x + s.q[pi]; v = t > 0.f ? t : 0.f; break; }
           case P_PRELU: { const float t = x + (s.q ? s.q[c] : 0.f); v = t > 0.f ? t : s.p[c] * t; break; }
           case P_PRELU_GRAD: { const float t = s.z[in_row * s.ldx + c] + (s.q ? s.q[c] : 0.f); v = x * (t > 0.f ? 1.f : s.p[c]); break; }
           case P_RELU: { const float t = x + (s.q ? s.q[c] : 0.f); v = t > 0.f ? t : 0.f; break; }
@@ -109,8 +110,8 @@ __global__ __launch_bounds__(256) void split3_v8_kernel(Split3Params s, long tot
         for (int e = 0; e < 4; ++e) { v[e] = x0[e]; v[4 + e] = x1[e]; }
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          pp[e] = s.p ? s.p[(s.op == P_AFFINE ? pi : c) + e] : 0.f;
-          qq[e] = s.q ? s.q[(s.op == P_AFFINE ? pi : c) + e] : 0.f;
+          pp[e] = s.p ? s.p[(s.op == P_AFFINE || s.op == P_AFFINE_RELU ? pi : c) + e] : 0.f;
+          qq[e] = s.q ? s.q[(s.op == P_AFFINE || s.op == P_AFFINE_RELU ? pi : c) + e] : 0.f;
           zz[e] = 0.f;
         }
         if (s.op == P_PRELU_GRAD || s.op == P_RELU_GRAD || s.op == P_QGELU_GRAD) {
@@ -125,6 +126,7 @@ __global__ __launch_bounds__(256) void split3_v8_kernel(Split3Params s, long tot
           float y;
           switch (s.op) {
             case P_AFFINE: y = pp[e] * v[e] + qq[e]; break;
+            case P_AFFINE_RELU: { const float t = pp[e] * v[e] + qq[e]; y = t > 0.f ? t : 0.f; break; }
             case P_PRELU: { const float t = v[e] + qq[e]; y = t > 0.f ? t : pp[e] * t; break; }
             case P_PRELU_GRAD: { const float t = zz[e] + qq[e]; y = v[e] * (t > 0.f ? 1.f : pp[e]); break; }
             case P_RELU: { const float t = v[e] + qq[e]; y = t > 0.f ? t : 0.f; break; }

@@ -131,6 +131,20 @@ _SIGS = {
                                      C.c_void_p]),
     "hedit_lpips_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hedit_faceparse_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "hedit_faceparse_destroy": (None, [C.c_void_p]),
+    "hedit_faceparse_num_params": (C.c_int, [C.c_void_p]),
+    "hedit_faceparse_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
+    "hedit_faceparse_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hedit_faceparse_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hedit_faceparse_missing": (C.c_int, [C.c_void_p]),
+    "hedit_faceparse_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hedit_faceparse_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "hedit_faceparse_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_size_t, C.c_void_p]),
+    "hedit_face_mask_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "hedit_face_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_size_t, C.c_void_p]),
     "hedit_vit_create": (C.c_int, [C.POINTER(VitCfg), C.POINTER(C.c_void_p)]),
     "hedit_vit_destroy": (None, [C.c_void_p]),
     "hedit_vit_num_params": (C.c_int, [C.c_void_p]),

@@ -8,9 +8,11 @@ Differences, all additive:
     and ./arcface/weights/model_ir_se50.pth); ``--random_init`` (``--tiny``) = synthetic weights.
   * the LPIPS term needs the third-party ``lpips`` package: used when importable, otherwise skipped (the loop guards
     ``lpipsloss=None`` exactly like the reference, h_edit_R.py:124).
-  * the post-processing face mask comes from the reference's face-parsing network (BiSeNet checkpoint), which is not
-    part of this build: pass ``--mask_dir DIR`` with precomputed label images ``<source stem>.png`` (face-parsing class
-    ids) to enable it; without it the result is saved unblended.
+  * the post-processing face mask (main_edit.py:120-127, :184-191, :211-212): as in the reference, the face-parsing U-Net
+    (``FaceParsing``, csrc/faceparse.hip) is loaded from ``./arcface/weights/face_parsing.pth`` relative to the working
+    directory, labels the source image, and ``face_mask`` turns the labels into SoftErosion(13, 0.9, 7)'s soft mask.
+    ``--mask_dir DIR`` with label images ``<source stem>.png`` (face-parsing class ids) takes precedence over the
+    network; with neither, the result is saved unblended.  The cosine similarity is printed for the blended image.
   * under torch.distributed.run the pairs are sharded over the ranks (one process per GPU).
 The ``ef`` baseline mode is refused."""
 import argparse
@@ -26,9 +28,8 @@ if HERE not in sys.path:
     sys.path.insert(0, HERE)
 
 from hedit import dist as D  # noqa: E402
-from hedit.arcface import IDLoss  # noqa: E402
+from hedit.arcface import FaceParsing, IDLoss, face_mask  # noqa: E402
 from hedit.arcface.arcface_model import load_face_image  # noqa: E402
-from hedit.arcface.face_utils import SoftErosion, encode_segmentation  # noqa: E402
 from hedit.diffusion import Model, TINY_DDPM_CONFIG  # noqa: E402
 from hedit.inversion.h_edit_R import h_Edit_R  # noqa: E402
 from hedit.inversion.sde_inversion import inversion_forward_process_sde  # noqa: E402
@@ -67,6 +68,40 @@ def build_parser():
     return p
 
 
+FACE_PARSING_CKPT = os.path.join(".", "arcface", "weights", "face_parsing.pth")     # main_edit.py:121, relative to the cwd
+
+
+def load_face_parser(args, device):
+    """the reference's face-parsing network when its checkpoint is present and --mask_dir is not given, else None.  Several
+    ranks: rank 0 reads the file, the others receive the tensors."""
+    if args.mask_dir or not os.path.exists(FACE_PARSING_CKPT):
+        return None
+    net = FaceParsing(device=device)      # training mode, as the reference leaves it: per-image BatchNorm statistics
+    net.load_state_dict(D.state_dict_from_rank0(lambda: torch.load(FACE_PARSING_CKPT, map_location="cpu"), net.param_shapes,
+                                                device=device))
+    return net
+
+
+def source_masks(args, face_parser, source_paths, sources, S):
+    """soft face masks (N, 1, S, S) of the source images (one call for the N of them), or None without a mask source"""
+    if args.mask_dir:
+        from PIL import Image
+        segs = []
+        for sp in source_paths:
+            lab = np.asarray(Image.open(os.path.join(args.mask_dir, os.path.splitext(os.path.basename(sp))[0] + ".png")))
+            seg = torch.from_numpy(lab.astype(np.int64))[None, None].to(sources.device)
+            if seg.shape[-1] != S:
+                seg = torch.nn.functional.interpolate(seg.float(), size=(S, S), mode="nearest").long()
+            segs.append(seg)
+        labels = torch.cat(segs)
+    elif face_parser is not None:
+        labels = face_parser(sources)
+    else:
+        return None
+    soft, _ = face_mask(labels, kernel_size=13, threshold=0.9, iterations=7)
+    return soft
+
+
 def linear_betas(device):
     return torch.from_numpy(np.linspace(0.0001, 0.02, 1000, dtype=np.float64)).float().to(device)
 
@@ -102,6 +137,7 @@ def main(argv=None):
     have_lpips = not args.no_lpips
     if have_lpips and not args.random_init and not args.lpips_ckpt:
         raise SystemExit("give --lpips_ckpt FILE (saved lpips.LPIPS(net='vgg').state_dict()), or --no_lpips")
+    face_parser = load_face_parser(args, device)
     pairs = list(get_source_ref_paths(args.json_file))
     written = []
     mine = D.shard(len(pairs), rank, world)
@@ -132,6 +168,9 @@ def main(argv=None):
                               weight_edit_face=args.weight_edit_face, optimization_steps=args.optimization_steps,
                               after_skip_steps=after_skip_steps, num_inference_steps=args.num_diffusion_steps, soft_face_mask=None,
                               per_image=True).detach()
+            masks = source_masks(args, face_parser, [sp for _, sp, _ in grp], torch.cat(srcs), S)
+            if args.post_processing and masks is not None:
+                edited = torch.cat([edited[k:k + 1] * masks[k:k + 1] + srcs[k] * (1 - masks[k:k + 1]) for k in range(len(grp))])
             with torch.no_grad():
                 print(f'Cosine Similarity: {idloss.get_cosine_sim(to256(edited)).mean().item()}')
             for k, (_, sp, rp) in enumerate(grp):
@@ -155,15 +194,7 @@ def main(argv=None):
         os.makedirs(save_path, exist_ok=True)
         xt, zs, xts, _ = inversion_forward_process_sde(model, source, betas, seq, etas=args.eta,
                                                        num_inference_steps=args.num_diffusion_steps, device=device)
-        soft_face_mask = None
-        if args.mask_dir:
-            from PIL import Image
-            lab = np.asarray(Image.open(os.path.join(args.mask_dir, os.path.splitext(os.path.basename(source_path))[0] + ".png")))
-            seg = torch.from_numpy(lab.astype(np.int64))[None, None].to(device)
-            if seg.shape[-1] != S:
-                seg = torch.nn.functional.interpolate(seg.float(), size=(S, S), mode="nearest").long()
-            enc = encode_segmentation(seg)
-            soft_face_mask, _ = SoftErosion(kernel_size=13, threshold=0.9, iterations=7).to(device)(enc[:, 0, None] + enc[:, 1, None])
+        soft_face_mask = source_masks(args, face_parser, [source_path], source, S)
         after_skip_steps = args.num_diffusion_steps - args.skip
         edited = h_Edit_R(model, lpipsloss, idloss, xts[after_skip_steps], betas, seq, eta=args.eta, zs=zs[:after_skip_steps],
                           weight_edit_face=args.weight_edit_face, optimization_steps=args.optimization_steps,

@@ -502,6 +502,41 @@ int hedit_vit_gram(hedit_vit* h, const float* image, int B, float* gram, void* w
 int hedit_vit_gram_fwd_bwd(hedit_vit* h, const float* image, const float* gram_ref, int ref_per_image, int B, float scale,
                            float* loss, float* d_image, void* workspace, size_t workspace_bytes, void* stream);
 
+
+/* ------------------------------------------------------------------------------------------------
+ * Face-parsing network of the face-swapping task: `FaceParsing()` of face-swapping/arcface/face_parsing_model.py
+ * (CelebAMask-HQ U-Net, feature_scale 4: filters 16/32/64/128/256, transposed-convolution up-sampling, BatchNorm,
+ * 19 classes, argmax) as main_edit.py:120-127 / :184 runs it.  Parameters by the reference's state_dict names
+ * (`conv1.conv1.0.weight`, `up_concat4.up.weight`, `final.bias`, ...; the integer `num_batches_tracked` buffers are
+ * not parameters), fp32 device tensors in torch layouts; hedit_faceparse_finalize packs the GEMM operands once.
+ * batch_stats = 1: every BatchNorm uses the (mean, biased variance) of each image over H x W -- the reference's model is
+ * never put in eval mode and is called with one image; results are bit-identical whatever the batch.  batch_stats = 0:
+ * the running statistics (eval mode).  H and W: positive multiples of 16. */
+typedef struct hedit_faceparse hedit_faceparse;
+int hedit_faceparse_create(hedit_faceparse** out);
+void hedit_faceparse_destroy(hedit_faceparse* h);
+int hedit_faceparse_num_params(const hedit_faceparse* h);
+const char* hedit_faceparse_param_name(const hedit_faceparse* h, int i);
+int hedit_faceparse_param_shape(const hedit_faceparse* h, int i, int* ndim, int* dims4);
+int hedit_faceparse_load(hedit_faceparse* h, const char* name, const float* dev_w, size_t numel, void* stream);
+int hedit_faceparse_missing(const hedit_faceparse* h);
+int hedit_faceparse_finalize(hedit_faceparse* h, void* stream);
+size_t hedit_faceparse_workspace_bytes(hedit_faceparse* h, int B, int height, int width);
+/* image fp32 [B][3][H][W] in [-1, 1] -> labels int64 [B][1][H][W] */
+int hedit_faceparse_labels(hedit_faceparse* h, const float* image, int B, int height, int width, int batch_stats,
+                           int64_t* labels, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Soft face mask of the face-swapping post-processing (main_edit.py:185-191): encode_segmentation's face + mouth map
+ * (face_utils.py: ids {1..7, 10, 11, 12}, the mouth 10 counted twice) through SoftErosion(kernel_size, threshold,
+ * iterations): iterations - 1 rounds of min(x, blur(x)), one more blur (zero-padded, normalised kernel_size^2 cone), then
+ * hard = x >= threshold -> 1, other pixels divided by their maximum.  The maximum is taken per image (the reference calls
+ * with one image).  No pixel below the threshold: soft = 1 everywhere; a maximum of 0: soft = 0 there.
+ * labels int64 [B][1][H][W] -> soft fp32, hard uint8 [B][1][H][W]; kernel_size odd in [3, 31] (1 makes the cone 0 / 0),
+ * iterations >= 1. */
+size_t hedit_face_mask_workspace_bytes(int B, int height, int width);
+int hedit_face_mask(const int64_t* labels, int B, int height, int width, int kernel_size, float threshold, int iterations,
+                    float* soft, uint8_t* hard, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
