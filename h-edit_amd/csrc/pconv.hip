@@ -163,9 +163,11 @@ __global__ __launch_bounds__(NT, 2) void pconv_kernel(GemmParams p) {
     wn = live ? n0 * p.K * 2 : 0;
   };
 #if defined(__HIP_DEVICE_COMPILE__)
+  // (each descriptor ends where its operand ends, as in igemm_kernel / pgemm_kernel: the A descriptor starts one input row early)
   const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<bf16_t*>(reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(p.A) - row_bytes)), (short)0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.W), (short)0, 0x7fffffff, 0x00020000);
+      const_cast<bf16_t*>(reinterpret_cast<const bf16_t*>(reinterpret_cast<const char*>(p.A) - row_bytes)), (short)0,
+      (int)((unsigned)row_bytes + p.a_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(p.W), (short)0, (int)p.w_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_c = __builtin_amdgcn_make_buffer_rsrc(p.C, (short)0, (int)((unsigned)p.M * ldc2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_b =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.bias), (short)0, p.bias ? p.N * 4 : 0, 0x00020000);   // no bias: every read is out of range = 0

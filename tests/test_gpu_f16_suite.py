@@ -57,6 +57,7 @@ SUITE = [
     ("test_gpu_clip.py", None, 5, 5),
     ("test_gpu_pnp.py", None, 4, 4),
     ("test_gpu_errors.py", None, 4, 4),
+    ("test_gpu_gemm_paths.py", None, 33, 33),
 ]
 
 
