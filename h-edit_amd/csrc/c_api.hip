@@ -85,6 +85,13 @@ int hedit_step_base(const float* eps, const float* xt, const float* z, float* x_
   return step_base_launch(eps, xt, z, x_prev, n_img, elems, eps_rows_per_img, to_coef(c), S(stream));
 } catch (...) { return hedit_abi_catch(); }
 
+int hedit_step_pair(const float* e_u, const float* e_c, const float* xt, const float* z, float* x_next, int n_img, int elems,
+                    int n_kinds, const hedit_step_coef* c, void* stream) try {
+  ARG_CHECK(e_u && e_c && xt && x_next && c && n_img > 0 && elems > 0 && (n_kinds == 1 || n_kinds == 2), "step_pair args");
+  const StepCoef k[2] = {to_coef(c), to_coef(c + (n_kinds - 1))};
+  return step_pair_launch(e_u, e_c, xt, z, x_next, n_img, elems, n_kinds, k, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
 int hedit_step_invert(const float* e_u, const float* e_c, const float* xt, float* x_prev, float* z_out, int n_img,
                       int elems, const hedit_step_coef* c, void* stream) try {
   ARG_CHECK(e_u && e_c && xt && x_prev && z_out && c && n_img > 0 && elems > 0, "step_invert args");

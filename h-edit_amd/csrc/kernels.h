@@ -247,6 +247,10 @@ struct StepCoef {
 // base pass: eps [rows][n_img][elems], rows = [x_o|null, x_e|null, x_o|src, x_e|src] -> x_prev [2][n_img][elems]
 int step_base_launch(const float* eps, const float* xt, const float* z, float* x_prev, int n_img,
                      int elems, int eps_rows_per_img, StepCoef c, hipStream_t st);
+// paired step of the comparison editors: e_u / e_c / xt / x_next [n_kinds][n_img][elems], z [n_img][elems] or null,
+// c[n_kinds] (w_src = that kind's CFG weight); step_base's arithmetic per element
+int step_pair_launch(const float* e_u, const float* e_c, const float* xt, const float* z, float* x_next, int n_img, int elems,
+                     int n_kinds, const StepCoef* c, hipStream_t st);
 // inversion step: z = (x_prev - mu) / sigma, x_prev <- mu + sigma z, with step_base's mu (sigma = c.noise_coef)
 int step_invert_launch(const float* e_u, const float* e_c, const float* xt, float* x_prev, float* z_out, int n_img,
                        int elems, StepCoef c, hipStream_t st);

@@ -54,6 +54,43 @@ __global__ __launch_bounds__(256) void step_base_kernel(const float* __restrict_
   }
 }
 
+// Paired CFG + reverse step of the gradient-free comparison editors (text-guided/inversion/p2p_baselines.py:165-181,
+// masactrl_baselines.py:76-92, pnp_baselines.py:301-307,375-391): source and target latent advance from the SAME pass
+// with their OWN guidance weight and stochasticity, so each kind carries its own coefficient set (c.w_src is that
+// kind's CFG weight), and both share the noise map z.  e_u / e_c / xt / x_next: [n_kinds][n_img][elems], z:
+// [n_img][elems] or NULL.  Per element it is step_base's arithmetic -- ddpm_mu, then pv + noise * z -- so on equal
+// coefficients it gives step_base's bits, and a source row fed the inversion's eps retraces step_invert's x_prev.
+// V = 4: 128-bit accesses (elems % 4 == 0 and 16-byte aligned bases, checked by the launcher).
+struct PairCoef { StepCoef k[2]; };
+
+template <int V>
+__global__ __launch_bounds__(256) void step_pair_kernel(const float* __restrict__ e_u, const float* __restrict__ e_c,
+                                                        const float* __restrict__ xt, const float* __restrict__ z,
+                                                        float* __restrict__ x_next, int n_img, int elems, PairCoef pc) {
+  const int img = blockIdx.y, kind = blockIdx.z;
+  const StepCoef c = pc.k[kind];
+  const long ro = ((long)kind * n_img + img) * elems, zo = (long)img * elems;
+  for (int i = (blockIdx.x * 256 + threadIdx.x) * V; i < elems; i += gridDim.x * 256 * V) {
+    alignas(16) float eu[V], ec[V], x[V], zz[V], o[V];
+    if (V == 4) {
+      *reinterpret_cast<float4*>(eu) = *reinterpret_cast<const float4*>(e_u + ro + i);
+      *reinterpret_cast<float4*>(ec) = *reinterpret_cast<const float4*>(e_c + ro + i);
+      *reinterpret_cast<float4*>(x) = *reinterpret_cast<const float4*>(xt + ro + i);
+      *reinterpret_cast<float4*>(zz) = z ? *reinterpret_cast<const float4*>(z + zo + i) : make_float4(0.f, 0.f, 0.f, 0.f);
+    } else {
+      eu[0] = e_u[ro + i]; ec[0] = e_c[ro + i]; x[0] = xt[ro + i]; zz[0] = z ? z[zo + i] : 0.f;
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      float pv = ddpm_mu(x[v], eu[v], ec[v], c);
+      pv = pv + c.noise_coef * zz[v];
+      o[v] = pv;
+    }
+    if (V == 4) *reinterpret_cast<float4*>(x_next + ro + i) = *reinterpret_cast<const float4*>(o);
+    else x_next[ro + i] = o[0];
+  }
+}
+
 // One step of the edit-friendly DDPM inversion (text-guided/inversion/ddpm_inversion.py:146-162):
 //   z = (x_prev - mu(x_t, e)) / sigma ;  x_prev <- mu + sigma z   (the reference's in-place rewrite of xts[idx]).
 // e_u / e_c: [n_img][elems] each (e_c == e_u for an unconditional inversion); sigma = c.noise_coef.
@@ -262,6 +299,22 @@ int step_base_launch(const float* eps, const float* xt, const float* z, float* x
   ARG_CHECK(rows == 4 || rows == 2, "step_base: eps rows per image must be 4 (P2P) or 2");
   dim3 grid(cdiv(elems, 256) > 64 ? 64 : cdiv(elems, 256), n_img);
   hipLaunchKernelGGL(step_base_kernel, grid, dim3(256), 0, st, eps, xt, z, x_prev, n_img, elems, rows, c);
+  LAUNCH_CHECK();
+  return HEDIT_OK;
+}
+
+int step_pair_launch(const float* e_u, const float* e_c, const float* xt, const float* z, float* x_next, int n_img, int elems,
+                     int n_kinds, const StepCoef* c, hipStream_t st) {
+  ARG_CHECK(n_kinds == 1 || n_kinds == 2, "step_pair: n_kinds must be 1 (one latent per image) or 2 (source, target)");
+  PairCoef pc;
+  pc.k[0] = c[0];
+  pc.k[1] = c[n_kinds - 1];
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+  const bool vec = elems % 4 == 0 && al16(e_u) && al16(e_c) && al16(xt) && al16(x_next) && (!z || al16(z));
+  const int per = vec ? cdiv(elems, 4) : elems;
+  dim3 grid(cdiv(per, 256) > 64 ? 64 : cdiv(per, 256), n_img, n_kinds);
+  if (vec) hipLaunchKernelGGL(step_pair_kernel<4>, grid, dim3(256), 0, st, e_u, e_c, xt, z, x_next, n_img, elems, pc);
+  else hipLaunchKernelGGL(step_pair_kernel<1>, grid, dim3(256), 0, st, e_u, e_c, xt, z, x_next, n_img, elems, pc);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }

@@ -368,6 +368,150 @@ class HEditEngine:
             xt = torch.cat([x_orig, x_k]).contiguous()
         return xt[n:].clone(), xt[:n].clone()
 
+    # ------------------------------------------------------------------ gradient-free comparison editors
+    def step_pair(self, e_u, e_c, xt, z, out, n, kinds, coefs):
+        """hedit_step_pair: e_u / e_c / xt / out [kinds][n][elems], z [n][elems] or None, one coefficient set per kind."""
+        elems = xt[0].numel()
+        for t_ in (e_u, e_c, xt, out) + (() if z is None else (z,)):
+            assert t_.is_contiguous() and t_.dtype == torch.float32
+        arr = (_lib.StepCoef * kinds)(*coefs)
+        _lib.check(self.lib.hedit_step_pair(_lib.ptr(e_u), _lib.ptr(e_c), _lib.ptr(xt), _lib.ptr(z), _lib.ptr(out), n, elems,
+                                            kinds, arr, _lib.cur_stream()))
+
+    def _pair_coefs(self, S, t, eta_i, ddim_inv, cfg_pair):
+        """(source, target) coefficient sets of one baseline step: the source row follows the inversion (eta, z), the
+        target row is deterministic for a DDIM inversion (PnP-Inv, p2p_baselines.py:176-179) and shares eta otherwise."""
+        return [S.step_coef(t, 0, eta_i, ddim_inv, (cfg_pair[0], 0.0, 0.0), coeff=0.0),
+                S.step_coef(t, 0, 0.0 if ddim_inv else eta_i, ddim_inv, (cfg_pair[-1], 0.0, 0.0), coeff=0.0)]
+
+    @torch.no_grad()
+    def run_direct(self, xT, zs, prompt_pairs, cfg_pair, controller=None, eta=1.0, after_skip_steps=None, ddim_inv=False,
+                   control=True):
+        """The comparison editors that sample source and target directly from one pass per step -- Edit Friendly and
+        PnP Inversion with P2P or MasaCtrl (text-guided/inversion/p2p_baselines.py:103-187, masactrl_baselines.py:15-94)
+        and Edit Friendly alone (p2p_baselines.py:19-95) -- for n images in lock-step.
+        xT (n,C,H,W); zs (T',n,C,H,W) or None; prompt_pairs n x [src, tar], or n x [tar] for the one-latent EF loop;
+        cfg_pair (cfg_src, cfg_tar), or (cfg_tar,) with one prompt.  Per step: the 4n-row pass [x_src|null]*n,
+        [x_tar|null]*n, [x_src|src]*n, [x_tar|tar]*n under ``controller`` (any object with _plan / _after_pass /
+        step_callback: P2P controllers, the MasaCtrl editor; control on, save_attn=True -- the reference calls the UNet
+        without kwargs there), then hedit_step_pair: the source row with (cfg_src, eta, z), the target row with
+        (cfg_tar, eta or 0 when ddim_inv, the same z), then step_callback.  control=False runs the pass plain.  With one
+        prompt per image: a plain 2n-row pass [x|null]*n, [x|tar]*n (the reference's two 1-row calls), one latent per
+        image, step_callback once after the loop (p2p_baselines.py:92-93).
+        Returns (edit, recon); recon is None for the one-latent loop."""
+        sch = self.model.scheduler
+        S = Schedule(sch)
+        T = sch.num_inference_steps
+        if after_skip_steps is None:
+            after_skip_steps = T
+        n = xT.shape[0]
+        dev = self.dev
+        pairs = [list(p) for p in prompt_pairs]
+        if len(pairs) != n or any(len(p) != len(pairs[0]) or len(p) not in (1, 2) for p in pairs):
+            raise ValueError("one [source, target] pair (or one [target]) per image expected")
+        kinds = len(pairs[0])
+        if len(cfg_pair) != kinds:
+            raise ValueError("one guidance weight per prompt expected")
+        xT = xT.to(device=dev, dtype=torch.float32)
+        if zs is not None:
+            zs = zs.to(device=dev, dtype=torch.float32).contiguous()
+        null = self.encode([""]).expand(n, -1, -1)
+        tar = self.encode([p[-1] for p in pairs])
+        if kinds == 2:
+            ctx = torch.cat([null, null, self.encode([p[0] for p in pairs]), tar]).contiguous()
+        else:
+            ctx = torch.cat([null, tar]).contiguous()
+        controlled = control and kinds == 2 and controller is not None
+
+        from .p2p.ptp_classes import runs_in_python
+        foreign = controlled and runs_in_python(controller)
+        if foreign:
+            if n != 1:
+                raise ValueError("a foreign controller runs one image at a time (it sees the reference's 4-row batch)")
+            if not callable(controller):
+                raise TypeError("a foreign controller must be callable as controller(attn, is_cross, place_in_unet, save_attn)")
+        step_cb = getattr(controller, "step_callback", None) if controller is not None else None
+        if step_cb is not None and not callable(step_cb):
+            raise TypeError("controller.step_callback must be callable as step_callback(x_t) -> x_t")
+
+        ts = [int(v) for v in sch.timesteps]
+        op = ts[-after_skip_steps:]
+        xt = torch.cat([xT] * kinds).contiguous()          # [x_src]*n, [x_tar]*n
+        H, W = xT.shape[2], xT.shape[3]
+        for i, t in enumerate(op):
+            idx = T - i - (T - after_skip_steps + 1)
+            z = zs[idx] if zs is not None else None
+            eta_i = float(eta[idx]) if isinstance(eta, (list, tuple)) else float(eta)
+            x_in = torch.cat([xt, xt])
+            if foreign:
+                e = self.unet.forward_hooked(x_in, t, ctx, controller, True)
+            elif controlled:
+                e = self.unet.forward_raw(x_in, t, ctx, controller._plan(self.unet, 4 * n, H, W, True))
+                controller._after_pass(True)
+            else:
+                e = self.unet.forward_raw(x_in, t, ctx, None)
+            coefs = self._pair_coefs(S, t, eta_i, ddim_inv, cfg_pair)
+            x_next = torch.empty_like(xt)
+            self.step_pair(e[:kinds * n], e[kinds * n:], xt, z, x_next, n, kinds, coefs[:kinds])
+            xt = x_next
+            if kinds == 2 and step_cb is not None:
+                xt = step_cb(xt)
+        if kinds == 1:
+            if step_cb is not None:
+                xt = step_cb(xt)
+            return xt.clone(), None
+        return xt[n:].clone(), xt[:n].clone()
+
+    @torch.no_grad()
+    def run_direct_pnp(self, xT, zs, prompts, cfg_pair, eta=0.0, after_skip_steps=None, ddim_inv=False, uncond="null"):
+        """The direct-sampling comparison editors with Plug-and-Play injection (text-guided/inversion/pnp_baselines.py:
+        negative_prompt_pnp :244-309, ef_or_pnp_inv_w_pnp :317-393) for n images in lock-step.  Per step: register_time,
+        one plain 2n-row pass [x_src|u]*n, [x_tar|u]*n for the unconditional rows -- u the null embedding, or the SOURCE
+        embedding for negative-prompt inversion (uncond="src", :293-294); the reference's two 1-row calls, to which
+        the hooks stay silent -- then the 2n-row pass [x_src|src]*n, [x_tar|tar]*n under the registered injection plan,
+        then hedit_step_pair with cfg_pair = (cfg of the source row, cfg of the target row).  Returns (edit, recon)."""
+        from .plug_n_play.pnp_utils import register_time
+        if uncond not in ("null", "src"):
+            raise ValueError("uncond must be 'null' or 'src'")
+        sch = self.model.scheduler
+        S = Schedule(sch)
+        T = sch.num_inference_steps
+        if after_skip_steps is None:
+            after_skip_steps = T
+        dev = self.dev
+        xT = xT.to(device=dev, dtype=torch.float32)
+        n = xT.shape[0]
+        pairs = [list(prompts[:2])] if isinstance(prompts[0], str) else [list(p[:2]) for p in prompts]
+        if len(pairs) != n:
+            raise ValueError("one [source, target] prompt pair per image expected")
+        if zs is not None:
+            zs = zs.to(device=dev, dtype=torch.float32).contiguous()
+            if zs.dim() == 4:
+                zs = zs[:, None]
+        src, tar = self.encode([p[0] for p in pairs]), self.encode([p[1] for p in pairs])
+        u = src if uncond == "src" else self.encode([""]).expand(n, -1, -1)
+        ctx_u = torch.cat([u, u]).contiguous()
+        ctx_pair = torch.cat([src, tar]).contiguous()
+        editor = getattr(self.unet, "_attention_editor", None)
+        ts = [int(v) for v in sch.timesteps]
+        op = ts[-after_skip_steps:]
+        xt = torch.cat([xT, xT]).contiguous()
+        H, W = xT.shape[2], xT.shape[3]
+        for i, t in enumerate(op):
+            idx = T - i - (T - after_skip_steps + 1)
+            z = zs[idx] if zs is not None else None
+            eta_i = float(eta[idx]) if isinstance(eta, (list, tuple)) else float(eta)
+            register_time(self.model, t)
+            e_u = self.unet.forward_raw(xt, t, ctx_u, None)
+            plan = editor._plan(self.unet, 2 * n, H, W, True, n_images=n) if editor is not None else None
+            e_c = self.unet.forward_raw(xt, t, ctx_pair, plan)
+            if editor is not None:
+                editor._after_pass(True)
+            x_next = torch.empty_like(xt)
+            self.step_pair(e_u, e_c, xt, z, x_next, n, 2, self._pair_coefs(S, t, eta_i, ddim_inv, cfg_pair))
+            xt = x_next
+        return xt[n:].clone(), xt[:n].clone()
+
     # ------------------------------------------------------------------ DDPM inversion
     @torch.no_grad()
     def ddpm_inversion(self, x0, prompts, eta=1.0, cfg_src=1.0, noise=None, generator=None, return_noise=False):

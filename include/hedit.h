@@ -182,6 +182,16 @@ int hedit_prof_records(hedit_unet* h, double* rows, int max_rows, int* n_rows);
  *   [n_img][2][heads][256][77]; alpha_layers [n_img][2][77]; enabled [n_img] or NULL. */
 int hedit_step_base(const float* eps, const float* xt, const float* z, float* x_prev, int n_img,
                     int elems, int eps_rows_per_img, const hedit_step_coef* c, void* stream);
+/* Paired CFG + reverse step of the gradient-free comparison editors (EF, PnP-Inv, NP;
+ * text-guided/inversion/p2p_baselines.py:165-181): source and target latent advance from the same UNet pass, each
+ * kind with its own coefficient set -- c[k].w_src is kind k's guidance weight, dir_coef / noise_coef its stochasticity.
+ *   e_u, e_c, xt, x_next: [n_kinds][n_img][elems], kind 0 = source (reconstruction), kind 1 = target (edit);
+ *   n_kinds = 1: one latent per image (EF without P2P);  z: [n_img][elems], shared by both kinds, or NULL;
+ *   c: HOST array of n_kinds coefficient sets.
+ * x_next = sqrt_ab_prev (x - sqrt_1m_ab_t e) / sqrt_ab_t + dir_coef e + noise_coef z,  e = e_u + w_src (e_c - e_u):
+ * the arithmetic of hedit_step_base element by element (same bits on equal coefficients). */
+int hedit_step_pair(const float* e_u, const float* e_c, const float* xt, const float* z, float* x_next, int n_img,
+                    int elems, int n_kinds, const hedit_step_coef* c, void* stream);
 /* inversion step: e_u, e_c, xt, x_prev (in/out), z_out: [n_img][elems]; sigma = c->noise_coef > 0; the CFG mix
  * uses c->w_src (pass e_c = e_u for an unconditional inversion). */
 int hedit_step_invert(const float* e_u, const float* e_c, const float* xt, float* x_prev, float* z_out,
