@@ -39,6 +39,10 @@ class VitCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("width", "layers", "heads", "patch_size", "input_resolution")]
 
 
+class TextCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("width", "layers", "heads", "vocab_size", "context_length", "proj_dim")]
+
+
 class P2PPlan(C.Structure):
     _fields_ = [("mode", C.c_int), ("n_pairs", C.c_int),
                 ("pair_src", C.c_void_p), ("pair_tar", C.c_void_p),
@@ -159,6 +163,17 @@ _SIGS = {
     "hedit_vit_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hedit_vit_gram_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hedit_text_create": (C.c_int, [C.POINTER(TextCfg), C.POINTER(C.c_void_p)]),
+    "hedit_text_destroy": (None, [C.c_void_p]),
+    "hedit_text_num_params": (C.c_int, [C.c_void_p]),
+    "hedit_text_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
+    "hedit_text_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hedit_text_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hedit_text_missing": (C.c_int, [C.c_void_p]),
+    "hedit_text_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hedit_text_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "hedit_text_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_size_t, C.c_void_p]),
     "hedit_vae_create": (C.c_int, [C.POINTER(VaeCfg), C.POINTER(C.c_void_p)]),
     "hedit_vae_destroy": (None, [C.c_void_p]),
     "hedit_vae_num_params": (C.c_int, [C.c_void_p]),

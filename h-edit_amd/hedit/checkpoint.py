@@ -15,7 +15,8 @@ import os
 import torch
 
 _WEIGHT_FILES = ("diffusion_pytorch_model.safetensors", "diffusion_pytorch_model.bin",
-                 "diffusion_pytorch_model.fp16.safetensors")
+                 "diffusion_pytorch_model.fp16.safetensors",
+                 "model.safetensors", "pytorch_model.bin", "model.fp16.safetensors")      # transformers' names (text_encoder/)
 
 
 def read_config(path):

@@ -144,7 +144,14 @@ class HEditEngine:
     def encode(self, prompts):
         """Prompt by prompt, each as a batch of one: the text encoder is a torch module whose GEMMs pick batch-dependent
         kernels, and an image's embedding must not depend on the prompts it happens to be batched with (the engine's
-        results are bit-identical across batch sizes, tests/test_gpu_invariance.py)."""
+        results are bit-identical across batch sizes, tests/test_gpu_invariance.py).  An encoder that says it is
+        ``batch_invariant`` (hedit.text.NativeClipText, csrc/text.hip) gives the bytes of single calls for a batch, so all
+        prompts go through ONE call."""
+        if getattr(self.model.text_encoder, "batch_invariant", False):
+            tok = self.model.tokenizer(list(prompts), padding="max_length", max_length=self.model.tokenizer.model_max_length,
+                                       truncation=True, return_tensors="pt")
+            with torch.no_grad():
+                return self.model.text_encoder(tok.input_ids)[0].float()      # validated on the host, uploaded by the encoder
         out = []
         for p in prompts:
             tok = self.model.tokenizer([p], padding="max_length", max_length=self.model.tokenizer.model_max_length,

@@ -18,17 +18,25 @@ class HEditPipeline:
         self.vae = vae
 
     @classmethod
-    def from_random(cls, config=None, seed=0, device="cuda:0", text_layers=12, vae_config=None, with_vae=False):
+    def from_random(cls, config=None, seed=0, device="cuda:0", text_layers=12, vae_config=None, with_vae=False, native_text=False):
         """SD-1.x-shaped pipeline with seeded synthetic weights (no checkpoints offline).
         ``with_vae`` adds the image autoencoder (hedit.vae.AutoencoderKL, SD-1.x shape unless
-        ``vae_config`` says otherwise)."""
+        ``vae_config`` says otherwise).  ``native_text``: the stand-in's weights run on the native prompt encoder
+        (hedit.text.NativeClipText, head dimension 64: ``heads = width // 64``) instead of the torch module."""
         cfg = dict(SD15_CONFIG)
         cfg.update(config or {})
+        dim = cfg["cross_attention_dim"]
+        if native_text and dim % 64:
+            raise ValueError(f"native_text: cross_attention_dim {dim} is not a multiple of the head dimension 64")
         unet = UNet2DConditionModel(cfg, device=device)
         unet.init_random(seed)
-        dim = cfg["cross_attention_dim"]
         heads = 12 if dim % 12 == 0 else 4
+        if native_text:
+            heads = dim // 64
         enc = ClipTextEncoder(dim=dim, layers=text_layers, heads=heads, seed=seed + 7).to(device)
+        if native_text:
+            from .text import NativeClipText
+            enc = NativeClipText.from_standin(enc, device=device)
         vae = None
         if with_vae or vae_config is not None:
             from .vae import AutoencoderKL
@@ -37,11 +45,13 @@ class HEditPipeline:
         return cls(unet, DDIMScheduler(), WordTokenizer(stable_ids=True), enc, vae, device)
 
     @classmethod
-    def from_pretrained(cls, path, device="cuda:0", tokenizer=None, text_encoder=None):
+    def from_pretrained(cls, path, device="cuda:0", tokenizer=None, text_encoder=None, native_text=False):
         """Load a LOCAL Stable-Diffusion-1.x checkpoint directory in the diffusers layout (what the
         reference's ``StableDiffusionPipeline.from_pretrained(model_id)`` resolves to,
         text-guided/main_p2p.py:104-106).  The UNet and VAE run on the HIP executors; the CLIP
-        text encoder / tokenizer are transformers' (PyTorch-ROCm), unless objects are passed in."""
+        text encoder / tokenizer are transformers' (PyTorch-ROCm), unless objects are passed in.
+        ``native_text``: ``<path>/text_encoder`` is read like the other components and runs on the native prompt
+        encoder (hedit.text.NativeClipText); transformers' CLIPTextModel is then never imported."""
         import os
         from . import checkpoint as CK
         from .vae import AutoencoderKL
@@ -75,6 +85,23 @@ class HEditPipeline:
         if tokenizer is None:
             from transformers import CLIPTokenizer
             tokenizer = CLIPTokenizer.from_pretrained(os.path.join(path, "tokenizer"), local_files_only=True)
+        if text_encoder is None and native_text:
+            from .text import NativeClipText, text_param_shapes
+            tdir = os.path.join(path, "text_encoder")
+            tcfg = CK.read_config(tdir)
+            multi = torch.distributed.is_available() and torch.distributed.is_initialized() and torch.distributed.get_world_size() > 1
+            if multi:
+                # the broadcast needs every rank to know names and shapes: the native table, filled on rank 0 from the file
+                # (a CLIPTextModel directory: no text_projection).  Every rank refuses an unsupported config by name first.
+                W, _ = NativeClipText.check_hf_config(tcfg)
+                shapes = text_param_shapes(W, int(tcfg["num_hidden_layers"]), int(tcfg["vocab_size"]), int(tcfg["max_position_embeddings"]))
+
+                def read_text():
+                    return NativeClipText.from_hf_state_dict(CK.read_component(tdir)[1], tcfg, device=device).state_dict()
+                tsd = HD.state_dict_from_rank0(read_text, shapes, device=device)
+                text_encoder = NativeClipText.from_clip_state_dict(tsd, device=device, eos_token_id=tcfg.get("eos_token_id"))
+            else:
+                text_encoder = NativeClipText.from_hf_state_dict(CK.read_component(tdir)[1], tcfg, device=device)
         if text_encoder is None:
             from transformers import CLIPTextModel
             text_encoder = CLIPTextModel.from_pretrained(os.path.join(path, "text_encoder"), local_files_only=True)

@@ -70,6 +70,9 @@ def build_parser():
     p.add_argument("--model_path", type=str, default=None, help="local SD-1.x checkpoint directory (diffusers layout)")
     p.add_argument("--random_init", action="store_true", help="synthetic SD-1.x-shaped weights (no checkpoint)")
     p.add_argument("--tiny", action="store_true", help="with --random_init: the small test configuration")
+    # opt-in, and absent from the namespace unless given (the parsed defaults stay the reference CLI + the additions above)
+    p.add_argument("--native_text", action="store_true", default=argparse.SUPPRESS,
+                   help="prompts through the native CLIP text encoder (csrc/text.hip), one call per lock-step group")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--batch", type=int, default=1, help="dataset entries edited in lock-step per pass")
     return p
@@ -82,11 +85,11 @@ def load_model(args, device):
             from hedit.vae import TINY_VAE_CONFIG
             vcfg = dict(TINY_VAE_CONFIG)
             vcfg.update(block_out_channels=(64, 64, 128, 128))          # f = 8 like SD
-            return HEditPipeline.from_random(TINY_CONFIG, seed=args.seed, device=device, text_layers=2, vae_config=vcfg)
-        return HEditPipeline.from_random(seed=args.seed, device=device, with_vae=True)
+            return HEditPipeline.from_random(TINY_CONFIG, seed=args.seed, device=device, text_layers=2, vae_config=vcfg, native_text=getattr(args, "native_text", False))
+        return HEditPipeline.from_random(seed=args.seed, device=device, with_vae=True, native_text=getattr(args, "native_text", False))
     if not args.model_path:
         raise SystemExit("give --model_path DIR (local diffusers-layout checkpoint) or --random_init")
-    return HEditPipeline.from_pretrained(args.model_path, device=device)
+    return HEditPipeline.from_pretrained(args.model_path, device=device, native_text=getattr(args, "native_text", False))
 
 
 def edit_group(args, model, entries, scale, size, device):

@@ -51,6 +51,9 @@ def build_parser():
     p.add_argument("--model_path", type=str, default=None, help="local SD-1.x checkpoint directory (diffusers layout)")
     p.add_argument("--random_init", action="store_true", help="synthetic SD-1.x-shaped weights (no checkpoint)")
     p.add_argument("--tiny", action="store_true", help="with --random_init: the small test configuration")
+    # opt-in, and absent from the namespace unless given (the parsed defaults stay the reference CLI + the additions above)
+    p.add_argument("--native_text", action="store_true", default=argparse.SUPPRESS,
+                   help="prompts through the native CLIP text encoder (csrc/text.hip), one call per lock-step group")
     p.add_argument("--seed", type=int, default=0)
     p.add_argument("--batch", type=int, default=1, help="dataset entries edited in lock-step per pass (batched engine)")
     return p
@@ -76,7 +79,7 @@ def load_pnp_model(args, device):
         ucfg["sample_size"] = 64
         vcfg = dict(TINY_VAE_CONFIG)
         vcfg.update(block_out_channels=(64, 64, 128))                 # f = 4: 256 x 256 images
-        return HEditPipeline.from_random(ucfg, seed=args.seed, device=device, text_layers=2, vae_config=vcfg)
+        return HEditPipeline.from_random(ucfg, seed=args.seed, device=device, text_layers=2, vae_config=vcfg, native_text=getattr(args, "native_text", False))
     return load_model(args, device)
 
 

@@ -512,6 +512,33 @@ int hedit_vit_gram(hedit_vit* h, const float* image, int B, float* gram, void* w
 int hedit_vit_gram_fwd_bwd(hedit_vit* h, const float* image, const float* gram_ref, int ref_per_image, int B, float scale,
                            float* loss, float* d_image, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Prompt encoder: `CLIP.encode_text` of text-guided-n-style/clip_guidance/clip/model.py:367-380 = transformers'
+ * CLIPTextModel of SD-1.x.  Token + positional embedding, `layers` pre-LN residual blocks with a causal mask (fused q/k/v
+ * projection, QuickGELU MLP), ln_final; forward only.  fp32 stream, split-bf16 contractions with fp32 accumulation; the
+ * result is batch-invariant bit for bit, position i depends on the tokens 0..i alone, and both storage builds give the
+ * same bits.  Parameters by the OpenAI CLIP state_dict names (`token_embedding.weight`, `positional_embedding`,
+ * `transformer.resblocks.{i}.attn.in_proj_weight`, ..., `ln_final.weight`, `text_projection` [width][proj_dim] when
+ * proj_dim > 0), fp32 device tensors; the token table stays fp32.  width / heads = 64; context_length <= 200; proj_dim 0
+ * (no text_projection) or a multiple of 4. */
+typedef struct hedit_text hedit_text;
+typedef struct { int width, layers, heads, vocab_size, context_length, proj_dim; } hedit_text_cfg;
+int hedit_text_create(const hedit_text_cfg* cfg, hedit_text** out);
+void hedit_text_destroy(hedit_text* h);
+int hedit_text_num_params(const hedit_text* h);
+const char* hedit_text_param_name(const hedit_text* h, int i);
+int hedit_text_param_shape(const hedit_text* h, int i, int* ndim, int* dims4);
+int hedit_text_load(hedit_text* h, const char* name, const float* dev_w, size_t numel, void* stream);
+int hedit_text_missing(const hedit_text* h);
+int hedit_text_finalize(hedit_text* h, void* stream);
+size_t hedit_text_workspace_bytes(hedit_text* h, int B, int L);
+/* ids int32 [B][L] (device, 1 <= L <= context_length; an id outside the table is clamped, never read out of bounds) ->
+ * hidden fp32 [B][L][width] after ln_final, or NULL;  pooled fp32 [B][proj_dim ? proj_dim : width] = the ln_final row at
+ * pool_index[b] (int32 [B], device), times text_projection when there is one, or NULL (then pool_index may be NULL).
+ * HEDIT_ERR_ARG, before anything is launched, for L or B out of range, a workspace below
+ * hedit_text_workspace_bytes(h, B, L), `pooled` without `pool_index`, or nothing to write. */
+int hedit_text_encode(hedit_text* h, const int32_t* ids, int B, int L, float* hidden, const int32_t* pool_index,
+                      float* pooled, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Face-parsing network of the face-swapping task: `FaceParsing()` of face-swapping/arcface/face_parsing_model.py
