@@ -7,11 +7,16 @@ Metrics.  The pixel metrics are computed here with the formulas of the torchmetr
 instantiates (evaluation/matrics_calculator.py:272-279): ``psnr`` (PeakSignalNoiseRatio(data_range=1)), ``mse``
 (MeanSquaredError), ``ssim`` (StructuralSimilarityIndexMeasure(data_range=1): 11 x 11 Gaussian window, sigma 1.5,
 k1 0.01, k2 0.03, reflect padding, mean over the interior), each on the whole image / the edited part / the unedited
-part exactly as the reference masks them (image * mask before the metric).  The network metrics need third-party
+part exactly as the reference masks them (image * mask before the metric).
+
+``clip_similarity_source_image`` / ``_target_image`` / ``_target_image_edit_part`` (torchmetrics CLIPScore on CLIP ViT-L/14,
+matrics_calculator.py:274,290-302) run on the native CLIP towers (hedit/clip_score.py, csrc/clipimg.hip + csrc/text.hip)
+when a LOCAL model is given with ``--clip_path`` (a transformers-style directory, or an OpenAI ``.pt`` together with
+``--clip_tokenizer DIR``) and ``--device cuda``; nothing is ever fetched.  The other network metrics need third-party
 checkpoints that do not exist offline and are not part of the sampling path (SURVEY.md section 8 row f4 "then the
-evaluator"): ``lpips*`` (torchmetrics LPIPS, SqueezeNet), ``clip_similarity_*`` / ``local_clip`` (CLIP ViT-L/14),
-``structure_distance*`` (DINO ViT-B/8 self-similarity) -- asking for one of them raises with the name of the
-missing checkpoint instead of writing a made-up number.
+evaluator"): ``lpips*`` (torchmetrics LPIPS, SqueezeNet), ``local_clip`` (prompt templates + CLIP RN50 / ViT-B/32),
+``structure_distance*`` (DINO ViT-B/8 self-similarity) -- asking for one of them, or for a CLIP score without a CLIP
+model, raises with the name of the missing checkpoint instead of writing a made-up number.
 """
 import argparse
 import csv
@@ -61,11 +66,33 @@ def _gauss(size=11, sigma=1.5):
     return (g[:, None] @ g[None, :])
 
 
-class MetricsCalculator:
-    """The pixel-metric half of the reference's MetricsCalculator (matrics_calculator.py:271-390), same method names."""
+def _require_cuda(device, what):
+    """the CLIP towers have no CPU execution path: say so instead of failing somewhere inside the library"""
+    if torch.device(device).type != "cuda":
+        raise RuntimeError(f"{what} on device {str(device)!r}: the CLIP towers run on the HIP executor only (there is no CPU path); "
+                           "use --device cuda")
 
-    def __init__(self, device="cpu"):
+
+class MetricsCalculator:
+    """The pixel metrics and the CLIP score of the reference's MetricsCalculator (matrics_calculator.py:271-390), same method
+    names.  `clip`: a CLIP scorer (hedit.clip_score.NativeClip); without one ``calculate_clip_similarity`` raises."""
+
+    def __init__(self, device="cpu", clip=None):
         self.device = device
+        self.clip = clip              # hedit.clip_score.NativeClip (or anything with score(uint8 H x W x 3 array, text)), or None
+        if clip is not None:
+            _require_cuda(device, "CLIP score")
+
+    def calculate_clip_similarity(self, img, txt, mask=None):
+        """matrics_calculator.py:290-302: the image (times the mask, back to uint8) and the prompt through CLIPScore"""
+        if self.clip is None:
+            raise NotImplementedError("clip similarity: needs " + NETWORK_METRICS["clip_similarity_target_image"] +
+                                      " (a local model: --clip_path), which this run does not have")
+        img = np.array(img)
+        if mask is not None:
+            mask = np.array(mask)
+            img = np.uint8(img * mask)
+        return float(self.clip.score(img, txt))
 
     def calculate_mse(self, img_pred, img_gt, mask_pred=None, mask_gt=None):
         a, b = _pair(img_pred, img_gt, mask_pred, mask_gt)
@@ -98,6 +125,14 @@ def calculate_metric(mc, metric, src_image, tgt_image, src_mask, tgt_mask, src_p
     for suffix in ("_unedit_part", "_edit_part"):
         if metric.endswith(suffix) and not metric.startswith("clip_similarity"):
             base, part = metric[:-len(suffix)], suffix
+    if metric.startswith("clip_similarity_") and metric in NETWORK_METRICS and getattr(mc, "clip", None) is not None:
+        if metric == "clip_similarity_source_image":
+            return mc.calculate_clip_similarity(src_image, src_prompt, None)
+        if metric == "clip_similarity_target_image":
+            return mc.calculate_clip_similarity(tgt_image, tgt_prompt, None)
+        if tgt_mask.sum() == 0:
+            return "nan"
+        return mc.calculate_clip_similarity(tgt_image, tgt_prompt, tgt_mask)
     if base in NETWORK_METRICS or metric in NETWORK_METRICS:
         raise NotImplementedError(f"metric {metric}: needs {NETWORK_METRICS.get(base, NETWORK_METRICS.get(metric))}, which this offline "
                                   "build does not have; pixel metrics: " + ", ".join(PIXEL_METRICS))
@@ -126,15 +161,34 @@ def build_parser():
     p.add_argument('--result_path', type=str, default="./results/results.csv")
     p.add_argument('--device', type=str, default="cpu")
     p.add_argument('--edit_category_list', nargs='+', type=str, default=[str(i) for i in range(10)])
+    p.add_argument('--clip_path', type=str, default=None,
+                   help="LOCAL CLIP model for the clip_similarity_* metrics: an openai/clip-vit-large-patch14-style directory "
+                        "(config.json, weights, tokenizer files) or an OpenAI .pt file (then also --clip_tokenizer)")
+    p.add_argument('--clip_tokenizer', type=str, default=None, help="local directory with the CLIP tokenizer files, for a bare .pt --clip_path")
     return p
 
 
-def main(argv=None):
+def load_clip(clip_path, clip_tokenizer, device):
+    """The native CLIP of --clip_path on `device` (local files only)"""
+    _require_cuda(device, "--clip_path")
+    from hedit.clip_score import NativeClip
+    dev = "cuda:0" if str(device) == "cuda" else device
+    if os.path.isdir(clip_path):
+        return NativeClip.from_pretrained(clip_path, device=dev)
+    if not clip_tokenizer:
+        raise SystemExit("--clip_path is a file (an OpenAI CLIP .pt): give --clip_tokenizer DIR with the tokenizer files")
+    return NativeClip.from_openai_checkpoint(clip_path, clip_tokenizer, device=dev)
+
+
+def main(argv=None, clip=None):
+    """`clip`: a ready CLIP scorer instead of --clip_path (synthetic runs and tests: NativeClip.from_standin)"""
     args = build_parser().parse_args(argv)
     if not args.tgt_folders or len(args.tgt_folders) != len(args.tgt_methods):
         raise SystemExit("give --tgt_folders DIR ... (one per method)")
     folders = dict(zip(args.tgt_methods, args.tgt_folders))
-    mc = MetricsCalculator(args.device)
+    if clip is None and args.clip_path:
+        clip = load_clip(args.clip_path, args.clip_tokenizer, args.device)
+    mc = MetricsCalculator(args.device, clip)
     os.makedirs(os.path.dirname(os.path.abspath(args.result_path)), exist_ok=True)
     with open(args.result_path, 'w', newline="") as f:
         csv.writer(f).writerow(["file_id"] + [f"{k}|{m}" for k in folders for m in args.metrics])
@@ -165,4 +219,6 @@ def main(argv=None):
 
 
 if __name__ == "__main__":
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # the `hedit` package, for --clip_path
     main()

@@ -43,6 +43,10 @@ class TextCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("width", "layers", "heads", "vocab_size", "context_length", "proj_dim")]
 
 
+class ClipImgCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("width", "layers", "heads", "patch_size", "input_resolution", "embed_dim")]
+
+
 class P2PPlan(C.Structure):
     _fields_ = [("mode", C.c_int), ("n_pairs", C.c_int),
                 ("pair_src", C.c_void_p), ("pair_tar", C.c_void_p),
@@ -174,6 +178,17 @@ _SIGS = {
     "hedit_text_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "hedit_text_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_size_t, C.c_void_p]),
+    "hedit_clipimg_create": (C.c_int, [C.POINTER(ClipImgCfg), C.POINTER(C.c_void_p)]),
+    "hedit_clipimg_destroy": (None, [C.c_void_p]),
+    "hedit_clipimg_num_params": (C.c_int, [C.c_void_p]),
+    "hedit_clipimg_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
+    "hedit_clipimg_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hedit_clipimg_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hedit_clipimg_missing": (C.c_int, [C.c_void_p]),
+    "hedit_clipimg_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hedit_clipimg_set_slices": (C.c_int, [C.c_void_p, C.c_int]),
+    "hedit_clipimg_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "hedit_clipimg_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hedit_vae_create": (C.c_int, [C.POINTER(VaeCfg), C.POINTER(C.c_void_p)]),
     "hedit_vae_destroy": (None, [C.c_void_p]),
     "hedit_vae_num_params": (C.c_int, [C.c_void_p]),

@@ -541,6 +541,39 @@ int hedit_text_encode(hedit_text* h, const int32_t* ids, int B, int L, float* hi
                       float* pooled, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * CLIP image tower: `CLIP.encode_image` of text-guided-n-style/clip_guidance/clip/model.py:202-236 = transformers'
+ * CLIPVisionModelWithProjection, the model of the PIE-Bench evaluator's CLIP score (text-guided/evaluation/
+ * matrics_calculator.py:274).  Patch embedding, class token + positional embedding, ln_pre, `layers` pre-LN residual
+ * blocks with bidirectional attention and a QuickGELU MLP, ln_post on the class row, times `visual.proj`; forward only.
+ * fp32 stream, split-bf16 contractions with fp32 accumulation; attention walks the keys in LDS tiles of 128 with an online
+ * softmax whose tile order is a function of the token count alone, so the result is batch-invariant bit for bit, does not
+ * depend on the slice count of the attention grid, and both storage builds give the same bits.  Parameters by the OpenAI
+ * CLIP state_dict names (`visual.conv1.weight`, `visual.class_embedding`, `visual.positional_embedding`, `visual.ln_pre.*`,
+ * `visual.transformer.resblocks.{i}.attn.in_proj_weight`, ..., `visual.ln_post.*`, `visual.proj` [width][embed_dim]), fp32
+ * device tensors.  width / heads = 64; (input_resolution / patch_size)^2 + 1 <= 577 tokens; embed_dim a multiple of 4. */
+#define HEDIT_CLIPIMG_MAX_BATCH 256
+typedef struct hedit_clipimg hedit_clipimg;
+typedef struct { int width, layers, heads, patch_size, input_resolution, embed_dim; } hedit_clipimg_cfg;
+int hedit_clipimg_create(const hedit_clipimg_cfg* cfg, hedit_clipimg** out);
+void hedit_clipimg_destroy(hedit_clipimg* h);
+int hedit_clipimg_num_params(const hedit_clipimg* h);
+const char* hedit_clipimg_param_name(const hedit_clipimg* h, int i);
+int hedit_clipimg_param_shape(const hedit_clipimg* h, int i, int* ndim, int* dims4);
+int hedit_clipimg_load(hedit_clipimg* h, const char* name, const float* dev_w, size_t numel, void* stream);
+int hedit_clipimg_missing(const hedit_clipimg* h);
+int hedit_clipimg_finalize(hedit_clipimg* h, void* stream);
+/* A TEST KNOB, not something a user ever needs: slices > 0 sets the number of workgroups the query rows of one (image, head)
+ * are dealt to (clamped to the number of 32-row passes); 0, the default: one per pass.  It sizes the attention grid only --
+ * the output bits do not depend on it, which is what the tests use it to show. */
+int hedit_clipimg_set_slices(hedit_clipimg* h, int slices);
+size_t hedit_clipimg_workspace_bytes(hedit_clipimg* h, int B);
+/* image fp32 [B][3][R][R] (device; resized, CLIP-normalised) -> out fp32 [B][embed_dim], not normalised.  HEDIT_ERR_ARG,
+ * before anything is launched, for B outside [1, HEDIT_CLIPIMG_MAX_BATCH] or a workspace below
+ * hedit_clipimg_workspace_bytes(h, B); creation refuses width / heads != 64 and more than 577 tokens the same way. */
+int hedit_clipimg_encode(hedit_clipimg* h, const float* image, int B, float* out, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Face-parsing network of the face-swapping task: `FaceParsing()` of face-swapping/arcface/face_parsing_model.py
  * (CelebAMask-HQ U-Net, feature_scale 4: filters 16/32/64/128/256, transposed-convolution up-sampling, BatchNorm,
  * 19 classes, argmax) as main_edit.py:120-127 / :184 runs it.  Parameters by the reference's state_dict names
