@@ -12,11 +12,14 @@ part exactly as the reference masks them (image * mask before the metric).
 ``clip_similarity_source_image`` / ``_target_image`` / ``_target_image_edit_part`` (torchmetrics CLIPScore on CLIP ViT-L/14,
 matrics_calculator.py:274,290-302) run on the native CLIP towers (hedit/clip_score.py, csrc/clipimg.hip + csrc/text.hip)
 when a LOCAL model is given with ``--clip_path`` (a transformers-style directory, or an OpenAI ``.pt`` together with
-``--clip_tokenizer DIR``) and ``--device cuda``; nothing is ever fetched.  The other network metrics need third-party
-checkpoints that do not exist offline and are not part of the sampling path (SURVEY.md section 8 row f4 "then the
-evaluator"): ``lpips*`` (torchmetrics LPIPS, SqueezeNet), ``local_clip`` (prompt templates + CLIP RN50 / ViT-B/32),
-``structure_distance*`` (DINO ViT-B/8 self-similarity) -- asking for one of them, or for a CLIP score without a CLIP
-model, raises with the name of the missing checkpoint instead of writing a made-up number.
+``--clip_tokenizer DIR``) and ``--device cuda``; nothing is ever fetched.  ``lpips`` / ``lpips_unedit_part`` /
+``lpips_edit_part`` (torchmetrics LPIPS with net_type='squeeze' on ``img * 2 - 1``, matrics_calculator.py:276,329-347) run
+on the native SqueezeNet-LPIPS (hedit/lpips_score.py, csrc/sqlpips.hip) when LOCAL weights are given with ``--lpips_path``
+(one state-dict file, or a directory holding the backbone file and the lin file) and ``--device cuda``.  The other network
+metrics need third-party checkpoints that do not exist offline and are not part of the sampling path (SURVEY.md section 8
+row f4 "then the evaluator"): ``local_clip`` (prompt templates + CLIP RN50 / ViT-B/32), ``structure_distance*`` (DINO
+ViT-B/8 self-similarity) -- asking for one of them, or for a CLIP score / LPIPS without its model, raises with the name of
+the missing checkpoint instead of writing a made-up number.
 """
 import argparse
 import csv
@@ -66,22 +69,34 @@ def _gauss(size=11, sigma=1.5):
     return (g[:, None] @ g[None, :])
 
 
-def _require_cuda(device, what):
-    """the CLIP towers have no CPU execution path: say so instead of failing somewhere inside the library"""
+def _require_cuda(device, what, who="the CLIP towers run"):
+    """the network metrics have no CPU execution path: say so instead of failing somewhere inside the library"""
     if torch.device(device).type != "cuda":
-        raise RuntimeError(f"{what} on device {str(device)!r}: the CLIP towers run on the HIP executor only (there is no CPU path); "
+        raise RuntimeError(f"{what} on device {str(device)!r}: {who} on the HIP executor only (there is no CPU path); "
                            "use --device cuda")
 
 
 class MetricsCalculator:
     """The pixel metrics and the CLIP score of the reference's MetricsCalculator (matrics_calculator.py:271-390), same method
-    names.  `clip`: a CLIP scorer (hedit.clip_score.NativeClip); without one ``calculate_clip_similarity`` raises."""
+    names.  `clip`: a CLIP scorer (hedit.clip_score.NativeClip); without one ``calculate_clip_similarity`` raises.  `lpips`:
+    an LPIPS scorer (hedit.lpips_score.NativeSqueezeLpips); without one ``calculate_lpips`` raises."""
 
-    def __init__(self, device="cpu", clip=None):
+    def __init__(self, device="cpu", clip=None, lpips=None):
         self.device = device
         self.clip = clip              # hedit.clip_score.NativeClip (or anything with score(uint8 H x W x 3 array, text)), or None
+        self.lpips = lpips            # hedit.lpips_score.NativeSqueezeLpips (or anything with score(pred, gt, mask_pred, mask_gt)), or None
         if clip is not None:
             _require_cuda(device, "CLIP score")
+        if lpips is not None:
+            _require_cuda(device, "LPIPS", "SqueezeNet-LPIPS runs")
+
+    def calculate_lpips(self, img_pred, img_gt, mask_pred=None, mask_gt=None):
+        """matrics_calculator.py:329-347: both images / 255, times their masks, * 2 - 1, through SqueezeNet-LPIPS (the
+        scorer does that preprocessing: it goes with the network's input convention)"""
+        if self.lpips is None:
+            raise NotImplementedError("lpips: needs " + NETWORK_METRICS["lpips"] + " (local files: --lpips_path), which this run does not have")
+        assert np.array(img_pred).shape == np.array(img_gt).shape, "Image shapes should be the same."
+        return float(self.lpips.score(img_pred, img_gt, mask_pred, mask_gt))
 
     def calculate_clip_similarity(self, img, txt, mask=None):
         """matrics_calculator.py:290-302: the image (times the mask, back to uint8) and the prompt through CLIPScore"""
@@ -133,10 +148,11 @@ def calculate_metric(mc, metric, src_image, tgt_image, src_mask, tgt_mask, src_p
         if tgt_mask.sum() == 0:
             return "nan"
         return mc.calculate_clip_similarity(tgt_image, tgt_prompt, tgt_mask)
-    if base in NETWORK_METRICS or metric in NETWORK_METRICS:
+    routed = PIXEL_METRICS + (("lpips",) if getattr(mc, "lpips", None) is not None else ())
+    if (base in NETWORK_METRICS or metric in NETWORK_METRICS) and base not in routed:
         raise NotImplementedError(f"metric {metric}: needs {NETWORK_METRICS.get(base, NETWORK_METRICS.get(metric))}, which this offline "
                                   "build does not have; pixel metrics: " + ", ".join(PIXEL_METRICS))
-    if base not in PIXEL_METRICS:
+    if base not in routed:
         raise ValueError(f"unknown metric {metric}")
     fn = getattr(mc, "calculate_" + base)
     if part is None:
@@ -165,6 +181,9 @@ def build_parser():
                    help="LOCAL CLIP model for the clip_similarity_* metrics: an openai/clip-vit-large-patch14-style directory "
                         "(config.json, weights, tokenizer files) or an OpenAI .pt file (then also --clip_tokenizer)")
     p.add_argument('--clip_tokenizer', type=str, default=None, help="local directory with the CLIP tokenizer files, for a bare .pt --clip_path")
+    p.add_argument('--lpips_path', type=str, default=None,
+                   help="LOCAL SqueezeNet-LPIPS weights for the lpips* metrics: one state-dict file (lpips / torchmetrics spelling), or a "
+                        "directory holding the backbone file (torchvision squeezenet1_1) and the lin file")
     return p
 
 
@@ -180,15 +199,25 @@ def load_clip(clip_path, clip_tokenizer, device):
     return NativeClip.from_openai_checkpoint(clip_path, clip_tokenizer, device=dev)
 
 
-def main(argv=None, clip=None):
-    """`clip`: a ready CLIP scorer instead of --clip_path (synthetic runs and tests: NativeClip.from_standin)"""
+def load_lpips(lpips_path, device):
+    """The native SqueezeNet-LPIPS of --lpips_path on `device` (local files only)"""
+    _require_cuda(device, "--lpips_path", "SqueezeNet-LPIPS runs")
+    from hedit.lpips_score import NativeSqueezeLpips
+    return NativeSqueezeLpips(lpips_path, device="cuda:0" if str(device) == "cuda" else device)
+
+
+def main(argv=None, clip=None, lpips=None):
+    """`clip` / `lpips`: ready scorers instead of --clip_path / --lpips_path (synthetic runs and tests:
+    NativeClip.from_standin, NativeSqueezeLpips())"""
     args = build_parser().parse_args(argv)
     if not args.tgt_folders or len(args.tgt_folders) != len(args.tgt_methods):
         raise SystemExit("give --tgt_folders DIR ... (one per method)")
     folders = dict(zip(args.tgt_methods, args.tgt_folders))
     if clip is None and args.clip_path:
         clip = load_clip(args.clip_path, args.clip_tokenizer, args.device)
-    mc = MetricsCalculator(args.device, clip)
+    if lpips is None and args.lpips_path:
+        lpips = load_lpips(args.lpips_path, args.device)
+    mc = MetricsCalculator(args.device, clip, lpips)
     os.makedirs(os.path.dirname(os.path.abspath(args.result_path)), exist_ok=True)
     with open(args.result_path, 'w', newline="") as f:
         csv.writer(f).writerow(["file_id"] + [f"{k}|{m}" for k in folders for m in args.metrics])
@@ -220,5 +249,5 @@ def main(argv=None, clip=None):
 
 if __name__ == "__main__":
     import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # the `hedit` package, for --clip_path
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # the `hedit` package, for --clip_path / --lpips_path
     main()

@@ -189,6 +189,17 @@ _SIGS = {
     "hedit_clipimg_set_slices": (C.c_int, [C.c_void_p, C.c_int]),
     "hedit_clipimg_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "hedit_clipimg_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hedit_sqlpips_create": (C.c_int, [C.POINTER(C.c_void_p)]),
+    "hedit_sqlpips_destroy": (None, [C.c_void_p]),
+    "hedit_sqlpips_num_params": (C.c_int, [C.c_void_p]),
+    "hedit_sqlpips_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
+    "hedit_sqlpips_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hedit_sqlpips_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hedit_sqlpips_missing": (C.c_int, [C.c_void_p]),
+    "hedit_sqlpips_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hedit_sqlpips_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "hedit_sqlpips_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_size_t, C.c_void_p]),
     "hedit_vae_create": (C.c_int, [C.POINTER(VaeCfg), C.POINTER(C.c_void_p)]),
     "hedit_vae_destroy": (None, [C.c_void_p]),
     "hedit_vae_num_params": (C.c_int, [C.c_void_p]),

@@ -574,6 +574,33 @@ int hedit_clipimg_encode(hedit_clipimg* h, const float* image, int B, float* out
                          void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * SqueezeNet-LPIPS, the `lpips*` columns of the PIE-Bench evaluator: LearnedPerceptualImagePatchSimilarity(net_type=
+ * 'squeeze') of text-guided/evaluation/matrics_calculator.py:276,329-347.  ScalingLayer (compiled in), torchvision
+ * squeezenet1_1.features with taps after features 1, 4, 7, 9, 10, 11, 12, every tap divided by its channel L2 norm + 1e-10,
+ * squared difference, 1x1 lin weights, spatial mean, sum over the seven taps; forward only.  Exact fp32 (direct FMA and the
+ * fp32 matrix instruction), fused Fire modules, no float atomics: dist[n] is bit-identical to the N = 1 call, symmetric in
+ * (a, b) bit for bit, exactly 0 for a = b, and both storage builds give the same bits.  Parameters by the torchvision names
+ * (`features.0.weight`, `features.{i}.squeeze|expand1x1|expand3x3.weight/.bias`, i in 3 4 6 7 9 10 11 12) and
+ * `lin{k}.model.1.weight` (k = 0..6), fp32 device tensors in torch layouts. */
+#define HEDIT_SQLPIPS_MAX_BATCH 64
+typedef struct hedit_sqlpips hedit_sqlpips;
+int hedit_sqlpips_create(hedit_sqlpips** out);
+void hedit_sqlpips_destroy(hedit_sqlpips* h);
+int hedit_sqlpips_num_params(const hedit_sqlpips* h);
+const char* hedit_sqlpips_param_name(const hedit_sqlpips* h, int i);
+int hedit_sqlpips_param_shape(const hedit_sqlpips* h, int i, int* ndim, int* dims4);
+int hedit_sqlpips_load(hedit_sqlpips* h, const char* name, const float* dev_w, size_t numel, void* stream);
+int hedit_sqlpips_missing(const hedit_sqlpips* h);
+int hedit_sqlpips_finalize(hedit_sqlpips* h, void* stream);
+size_t hedit_sqlpips_workspace_bytes(hedit_sqlpips* h, int N, int height, int width);
+/* a, b fp32 [N][3][H][W] in [-1, 1] (device) -> dist fp32 [N], dist[n] = LPIPS(a_n, b_n).  HEDIT_ERR_STATE for a handle
+ * that is not finalized, HEDIT_ERR_ARG for H or W outside [32, 4096] (no multiple-of-16 rule), N outside
+ * [1, HEDIT_SQLPIPS_MAX_BATCH] or a workspace below hedit_sqlpips_workspace_bytes(h, N, H, W): all before anything is
+ * launched. */
+int hedit_sqlpips_distance(hedit_sqlpips* h, const float* a, const float* b, int N, int height, int width, float* dist,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Face-parsing network of the face-swapping task: `FaceParsing()` of face-swapping/arcface/face_parsing_model.py
  * (CelebAMask-HQ U-Net, feature_scale 4: filters 16/32/64/128/256, transposed-convolution up-sampling, BatchNorm,
  * 19 classes, argmax) as main_edit.py:120-127 / :184 runs it.  Parameters by the reference's state_dict names
