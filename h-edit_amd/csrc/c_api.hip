@@ -410,4 +410,62 @@ int hedit_k_f32_to_bf16(const float* x, void* y, int64_t n, void* stream) try {
   return f32_to_bf16_launch(x, reinterpret_cast<bf16_t*>(y), (long)n, S(stream));
 } catch (...) { return hedit_abi_catch(); }
 
+// ---- the decoder's backward pieces (grad.hip) and the forward kernels that feed them statistics and probabilities
+int hedit_k_groupnorm_stats(const void* x, void* y, const float* gamma, const float* beta, int B, int HW, int C, int G,
+                            float eps, int silu, void* ws, float* stats, void* stream) try {
+  ARG_CHECK(x && y && gamma && beta && ws && stats, "groupnorm_stats args");
+  return groupnorm_launch(reinterpret_cast<const bf16_t*>(x), reinterpret_cast<bf16_t*>(y), gamma, beta, B, HW, C, G,
+                          eps, silu, reinterpret_cast<float*>(ws), S(stream), stats);
+} catch (...) { return hedit_abi_catch(); }
+
+size_t hedit_k_groupnorm_bwd_ws_bytes(int B, int HW, int C) { return groupnorm_bwd_ws_bytes(B, HW, C); }
+
+int hedit_k_groupnorm_bwd(const void* x, const void* dy, const void* add, void* dx, const float* gamma, const float* beta,
+                          const float* stats, int B, int HW, int C, int G, int silu, void* ws, void* stream) try {
+  ARG_CHECK(x && dy && dx && gamma && beta && stats && ws, "groupnorm_bwd args");
+  return groupnorm_bwd_launch(reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(dy),
+                              reinterpret_cast<const bf16_t*>(add), reinterpret_cast<bf16_t*>(dx), gamma, beta, stats, B, HW, C,
+                              G, silu, reinterpret_cast<float*>(ws), S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_softmax_rows(const float* s, void* p, int64_t rows, int N, float scale, void* stream) try {
+  ARG_CHECK(s && p, "softmax_rows args");
+  return softmax_rows_launch(s, reinterpret_cast<bf16_t*>(p), (long)rows, N, scale, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_softmax_blockdiag(const float* s, void* p, int64_t rows, int T, int ld, float scale, void* stream) try {
+  ARG_CHECK(s && p, "softmax_blockdiag args");
+  return softmax_blockdiag_launch(s, reinterpret_cast<bf16_t*>(p), (long)rows, T, ld, scale, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_softmax_bwd(const void* p, const float* dp, void* ds, int64_t rows, int N, float scale, void* stream) try {
+  ARG_CHECK(p && dp && ds, "softmax_bwd args");
+  return softmax_bwd_launch(reinterpret_cast<const bf16_t*>(p), dp, reinterpret_cast<bf16_t*>(ds), (long)rows, N, scale, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_transpose(const void* src, void* dst, int R, int C, void* stream) try {
+  ARG_CHECK(src && dst, "transpose args");
+  return transpose_bf16_launch(reinterpret_cast<const bf16_t*>(src), reinterpret_cast<bf16_t*>(dst), R, C, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_sum2x2(const void* du, void* dx, int B, int H, int W, int C, void* stream) try {
+  ARG_CHECK(du && dx, "sum2x2 args");
+  return sum2x2_launch(reinterpret_cast<const bf16_t*>(du), reinterpret_cast<bf16_t*>(dx), B, H, W, C, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_pack_conv3x3_dgrad(const float* w, void* out, int O, int I, void* stream) try {
+  ARG_CHECK(w && out, "pack args");
+  return pack_conv3x3_dgrad_launch(w, reinterpret_cast<bf16_t*>(out), O, I, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_pack_linear_t(const float* w, void* out, int O, int I, void* stream) try {
+  ARG_CHECK(w && out, "pack args");
+  return pack_linear_t_launch(w, reinterpret_cast<bf16_t*>(out), O, I, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_flip_oihw(const float* w, float* out, int O, int I, int k, void* stream) try {
+  ARG_CHECK(w && out, "flip args");
+  return flip_oihw_launch(w, out, O, I, k, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
 }  // extern "C"

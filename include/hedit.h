@@ -402,6 +402,35 @@ int hedit_k_attn_apply(const float* probs, const void* vt, int64_t ldvt, void* o
                        int kstride, int heads, int d, void* stream);
 int hedit_k_pack_conv3x3(const float* w_oihw, void* out, int O, int I, void* stream);
 int hedit_k_f32_to_bf16(const float* x, void* y, int64_t n, void* stream);
+/* The pieces of the image decoder's input-gradient pass (csrc/grad.hip; tests/test_gpu_grad_kernels.py), one launcher each,
+ * and the forward kernels that feed them statistics and probabilities.  x / y / dy / dx / add / p / ds / du / src / dst and the
+ * packed weights are bf16, NHWC where they are images; scores, dp, statistics and checkpoint weights are fp32.
+ * hedit_k_groupnorm_stats: hedit_k_groupnorm that also writes stats [B][G][2] = (mean, rstd) per image and group, the buffer
+ *   the backward pass is given; same ws, the same bits in y.
+ * hedit_k_groupnorm_bwd: dx = d GroupNorm(+SiLU)(x) / dx applied to dy (+ add, or NULL): t = dz gamma,
+ *   dx = rstd (t - mean_g(t) - xh mean_g(t xh)).  C % 8 == 0, C % G == 0, G <= 64, C / 8 a divisor of 256;
+ *   ws of hedit_k_groupnorm_bwd_ws_bytes.
+ * hedit_k_softmax_rows: p [rows][N] = softmax(scale * s) by rows, N % 4 == 0.  hedit_k_softmax_blockdiag: images of T tokens
+ *   stacked along both axes of s [rows][ld]: the softmax inside each image's diagonal block, exact zeros elsewhere
+ *   (T % 4, ld % 4, rows % T == 0).  hedit_k_softmax_bwd: ds = scale * p * (dp - rowsum(dp * p)), N % 4 == 0.
+ * hedit_k_transpose: dst [C][R] = src [R][C]^T, R % 64 == 0 and C % 64 == 0.
+ * hedit_k_sum2x2: dx [B][H][W][C] = the 2x2 block sums of du [B][2H][2W][C] (backward of the nearest 2x upsample), C % 8 == 0.
+ * Weights of the input-gradient GEMMs from the checkpoint's fp32 tensors: hedit_k_pack_conv3x3_dgrad OIHW -> bf16 [I][9][O]
+ *   with the taps flipped (the weight of hedit_k_gemm mode 1 with the channel counts swapped); hedit_k_pack_linear_t
+ *   [O][I] -> bf16 [I][O]; hedit_k_flip_oihw k x k OIHW -> fp32 IOHW with the taps flipped. */
+int hedit_k_groupnorm_stats(const void* x, void* y, const float* gamma, const float* beta, int B, int HW, int C, int G,
+                            float eps, int silu, void* ws, float* stats, void* stream);
+size_t hedit_k_groupnorm_bwd_ws_bytes(int B, int HW, int C);
+int hedit_k_groupnorm_bwd(const void* x, const void* dy, const void* add, void* dx, const float* gamma, const float* beta,
+                          const float* stats, int B, int HW, int C, int G, int silu, void* ws, void* stream);
+int hedit_k_softmax_rows(const float* s, void* p, int64_t rows, int N, float scale, void* stream);
+int hedit_k_softmax_blockdiag(const float* s, void* p, int64_t rows, int T, int ld, float scale, void* stream);
+int hedit_k_softmax_bwd(const void* p, const float* dp, void* ds, int64_t rows, int N, float scale, void* stream);
+int hedit_k_transpose(const void* src, void* dst, int R, int C, void* stream);
+int hedit_k_sum2x2(const void* du, void* dx, int B, int H, int W, int C, void* stream);
+int hedit_k_pack_conv3x3_dgrad(const float* w_oihw, void* out, int O, int I, void* stream);
+int hedit_k_pack_linear_t(const float* w, void* out, int O, int I, void* stream);
+int hedit_k_flip_oihw(const float* w_oihw, float* out, int O, int I, int k, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Pixel-space DDPM UNet of the face-swapping task: `Model.forward(x, t)` of
