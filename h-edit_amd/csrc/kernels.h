@@ -136,8 +136,16 @@ bool splitk_reduce_ln_supported(int C);
 int splitk_reduce_ln_launch(const float* partial, int splits, const float* bias, const bf16_t* residual, int ldr, bf16_t* out,
                             bf16_t* y, const float* gamma, const float* beta, long rows, int C, float eps, hipStream_t st);
 int geglu_launch(const bf16_t* x, bf16_t* y, long rows, int inner, hipStream_t st);
+// A batch-row map handed to kernels BY VALUE (kernel arguments: no upload, no host stall): row b of the batch reads row
+// src[b] of a tensor that holds each distinct row once (hedit_unet_forward_shared).
+#define HEDIT_ROWMAP_MAX 512
+struct RowMap { uint16_t src[HEDIT_ROWMAP_MAX]; };
 // y [rows][ca+cb] = [a | b]; a == nullptr: the left part is already in place, only b is copied
-int concat_launch(const bf16_t* a, int ca, const bf16_t* b, int cb, bf16_t* y, long rows, hipStream_t st);
+// b_map: image i of b (rows_per_image rows each) is image b_map->src[i] of a tensor with fewer images
+int concat_launch(const bf16_t* a, int ca, const bf16_t* b, int cb, bf16_t* y, long rows, hipStream_t st,
+                  const RowMap* b_map = nullptr, int rows_per_image = 0);
+// dst[t][b] <- src[t][map.src[b]] for t < n <= 3 tensors of B rows of row_bytes bytes each (a multiple of 16, 16-byte-aligned bases): one launch
+int gather_rows_launch(const void* const* src, void* const* dst, int n, int B, long row_bytes, const RowMap& map, hipStream_t st);
 int f32_to_bf16_launch(const float* x, bf16_t* y, long n, hipStream_t st);
 int ctx_pad_launch(const float* x, bf16_t* y, int B, int dim, hipStream_t st);
 // out[n] = sum_k W[n][k] * act(x[k]) + b0[n] + b1[n]   (act = SiLU if silu), x/out fp32, W bf16

@@ -424,6 +424,32 @@ __global__ __launch_bounds__(256) void concat_kernel(const bf16_t* __restrict__ 
   }
 }
 
+// [a | b] with image i of b taken from image map.src[i] of a tensor that holds each distinct image once; a == nullptr: only
+// the right cb columns are written (the left ones are in place)
+__global__ __launch_bounds__(256) void concat_mapped_kernel(const bf16_t* __restrict__ a, int ca, const bf16_t* __restrict__ b, int cb,
+                                                            bf16_t* __restrict__ y, long rows, int rows_per_image, RowMap map) {
+  const int AV = a ? ca / 8 : 0, BV = cb / 8, CV = AV + BV;
+  const long total = rows * CV;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long row = i / CV;
+    const int v = (int)(i - row * CV);
+    const long img = row / rows_per_image;
+    const long brow = (long)map.src[img] * rows_per_image + (row - img * rows_per_image);
+    uint4 u = v < AV ? *reinterpret_cast<const uint4*>(a + row * ca + v * 8)
+                     : *reinterpret_cast<const uint4*>(b + brow * cb + (v - AV) * 8);
+    *reinterpret_cast<uint4*>(y + row * (ca + cb) + (a ? 0 : ca) + v * 8) = u;
+  }
+}
+
+// dst[t][b] <- src[t][map.src[b]]: blockIdx.y = batch row, blockIdx.z = tensor; rows of row_v 16-byte lanes
+struct GatherRows { const uint4* src[3]; uint4* dst[3]; long row_v; };
+__global__ __launch_bounds__(256) void gather_rows_kernel(GatherRows g, RowMap map) {
+  const int b = blockIdx.y, t = blockIdx.z;
+  const uint4* __restrict__ from = g.src[t] + (long)map.src[b] * g.row_v;
+  uint4* __restrict__ to = g.dst[t] + (long)b * g.row_v;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < g.row_v; i += (long)gridDim.x * 256) to[i] = from[i];
+}
+
 __global__ __launch_bounds__(256) void f32_to_bf16_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, long n, float scale) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256)
     y[i] = f32_to_bf16(x[i] * scale);
@@ -860,14 +886,39 @@ int geglu_launch(const bf16_t* x, bf16_t* y, long rows, int inner, hipStream_t s
   return HEDIT_OK;
 }
 
-int concat_launch(const bf16_t* a, int ca, const bf16_t* b, int cb, bf16_t* y, long rows, hipStream_t st) {
+int concat_launch(const bf16_t* a, int ca, const bf16_t* b, int cb, bf16_t* y, long rows, hipStream_t st, const RowMap* b_map,
+                  int rows_per_image) {
   ARG_CHECK(ca % 8 == 0 && cb % 8 == 0, "concat: channels % 8");
+  if (b_map) {
+    ARG_CHECK(rows_per_image > 0 && rows % rows_per_image == 0 && rows / rows_per_image <= HEDIT_ROWMAP_MAX, "concat: row map");
+    hipLaunchKernelGGL(concat_mapped_kernel, dim3(ew_grid(rows * (((a ? ca : 0) + cb) / 8))), dim3(256), 0, st, a, ca, b, cb, y, rows,
+                       rows_per_image, *b_map);
+    LAUNCH_CHECK();
+    return HEDIT_OK;
+  }
   if (a == nullptr) {
     hipLaunchKernelGGL(concat_right_kernel, dim3(ew_grid(rows * (cb / 8))), dim3(256), 0, st, b, ca, cb, y, rows);
     LAUNCH_CHECK();
     return HEDIT_OK;
   }
   hipLaunchKernelGGL(concat_kernel, dim3(ew_grid(rows * ((ca + cb) / 8))), dim3(256), 0, st, a, ca, b, cb, y, rows);
+  LAUNCH_CHECK();
+  return HEDIT_OK;
+}
+
+int gather_rows_launch(const void* const* src, void* const* dst, int n, int B, long row_bytes, const RowMap& map, hipStream_t st) {
+  ARG_CHECK(n >= 1 && n <= 3 && B >= 1 && B <= HEDIT_ROWMAP_MAX, "gather_rows: tensors / rows");
+  ARG_CHECK(row_bytes > 0 && row_bytes % 16 == 0, "gather_rows: row size must be a multiple of 16 bytes");
+  GatherRows g{};
+  for (int t = 0; t < n; ++t) {
+    ARG_CHECK(src[t] && dst[t] && (reinterpret_cast<uintptr_t>(src[t]) | reinterpret_cast<uintptr_t>(dst[t])) % 16 == 0,
+              "gather_rows: tensors must be 16-byte aligned");
+    g.src[t] = reinterpret_cast<const uint4*>(src[t]);
+    g.dst[t] = reinterpret_cast<uint4*>(dst[t]);
+  }
+  g.row_v = row_bytes / 16;
+  const int gx = ew_grid(g.row_v) > 64 ? 64 : ew_grid(g.row_v);
+  hipLaunchKernelGGL(gather_rows_kernel, dim3(gx, B, n), dim3(256), 0, st, g, map);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }

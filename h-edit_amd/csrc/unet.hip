@@ -5,6 +5,7 @@
 //
 // Architecture = diffusers' UNet2DConditionModel as used by SD-1.4/1.5;
 // parameter names are the diffusers state_dict keys so real checkpoints load unchanged.
+#include <array>
 #include <map>
 #include <string>
 #include <vector>
@@ -96,6 +97,9 @@ struct hedit_unet {
   // instead of two small launches per block (32 per call on SD-1.x)
   bf16_t *wk2_all = nullptr, *wv2_all = nullptr;
   int ctx_n = 0, ctx_next = 0;
+  // hedit_unet_workspace_bytes by (B, height, width, hook set): the answer covers every row map, i.e. one dry run per
+  // number of distinct latents, so it is worked out once per shape
+  std::map<std::array<int, 4>, size_t> ws_cache;
 };
 
 namespace {
@@ -256,7 +260,19 @@ struct Fwd {
   int rblock = 0;            // ResNet blocks visited so far (PnP feature injection)
   int place = 0;             // 0 down, 1 mid, 2 up: where the transformer block being executed sits (the hook's argument)
   int hook_layer = 0;        // attention layers handed to the hook so far in this call
+  const RowMap* map = nullptr;   // hedit_unet_forward_shared: batch row -> distinct latent (null in a dry run)
   bool dry() const { return ar.dry; }
+};
+
+// The rows of one latent stay identical until the first cross-attention, so that part runs once per DISTINCT latent: the
+// helpers take the batch from f.B, which this guard sets for a scope -- on the one Fwd, whose arena goes on.
+struct BatchScope {
+  Fwd& f;
+  int saved;
+  BatchScope(Fwd& f_, int rows) : f(f_), saved(f_.B) { f.B = rows; }
+  ~BatchScope() { f.B = saved; }
+  BatchScope(const BatchScope&) = delete;
+  BatchScope& operator=(const BatchScope&) = delete;
 };
 
 #define RUN(f, expr)            \
@@ -437,21 +453,24 @@ int hooked_attention(Fwd& f, const bf16_t* q, int ldq, const bf16_t* k, int ldk,
   return HEDIT_OK;
 }
 
-// x [M][C] -> *out [M][C] (allocated here; x is NOT freed)
-int transformer(Fwd& f, const Attn& a, const bf16_t* x, int H, int W, bf16_t** out, bf16_t* dst = nullptr, int ldd = 0) {
+void chain_prof(Fwd& f, ProfScope& ps, size_t M, int C, int layers, int tag) {
+  if (ps.rec >= 0) {
+    auto& r = f.h->prof_recs[ps.rec];
+    r.m = (int)M; r.n = C; r.k = layers * C; r.tag = tag;
+  }
+}
+
+// A transformer block in two halves.  transformer_stem: everything in front of the cross-attention -- GroupNorm, proj_in,
+// norm1, the self-attention, attn1.to_out + residual, norm2, attn2.to_q.  None of it sees the text context, so rows that
+// carry the same latent give the same *t1 (the residual stream) and *q2 (the cross-attention's query), both [M][C] and
+// allocated here; x is NOT freed.
+int transformer_stem(Fwd& f, const Attn& a, const bf16_t* x, int H, int W, bf16_t** t1_out, bf16_t** q2_out) {
   const int C = a.C, N = H * W, B = f.B, heads = f.h->cfg.heads, d = C / heads;
-  const int ctx_dim = f.h->cfg.cross_attention_dim;
   const size_t M = (size_t)B * N;
   const hedit_p2p_plan* pl = (f.plan && f.plan->mode > 0) ? f.plan : nullptr;
-  bf16_t *xn, *t0, *tn, *qk, *vt, *ao, *t1, *q2, *k2, *vt2, *t2, *gf, *t3, *y;
+  bf16_t *xn, *t0, *tn, *qk, *vt, *ao, *t1, *q2;
 
   const bool chain = a.ffs != nullptr;
-  auto chain_prof = [&](ProfScope& ps, int layers, int tag) {
-    if (ps.rec >= 0) {
-      auto& r = f.h->prof_recs[ps.rec];
-      r.m = (int)M; r.n = C; r.k = layers * C; r.tag = tag;
-    }
-  };
   TRY(aalloc(f, &t0, M * C));
   TRY(aalloc(f, &qk, M * 2 * C));
   TRY(aalloc(f, &vt, M * C));
@@ -469,7 +488,7 @@ int transformer(Fwd& f, const Attn& a, const bf16_t* x, int H, int W, bf16_t** o
     lc.M = (int)M; lc.C = C;
     {
       ProfScope ps(f, PK_LINEAR, 2.0 * M * 4.0 * C * C, 10.0 * M * C + 8.0 * C * C);      // x read; t0, q, k, v^T written; weights once
-      chain_prof(ps, 4, 129);                                                               // tag 129: GroupNorm .. q | k | v^T
+      chain_prof(f, ps, M, C, 4, 129);                                                   // tag 129: GroupNorm .. q | k | v^T
       RUN(f, lin_chain_launch(lc, f.st));
     }
     f.ar.free(ws);
@@ -523,7 +542,7 @@ int transformer(Fwd& f, const Attn& a, const bf16_t* x, int H, int W, bf16_t** o
     lc.gamma = a.ln2g; lc.beta = a.ln2b; lc.eps = 1e-5f; lc.stream = a.k1s;
     lc.out_mid = t1; lc.ldmid = C; lc.out = q2; lc.ldo = C; lc.M = (int)M; lc.C = C;
     ProfScope ps(f, PK_LINEAR, 2.0 * M * 2.0 * C * C, 8.0 * M * C + 4.0 * C * C);          // ao, t0 read; t1, q written
-    chain_prof(ps, 2, 130);                                                                 // tag 130: attn1.to_out .. attn2.to_q
+    chain_prof(f, ps, M, C, 2, 130);                                                     // tag 130: attn1.to_out .. attn2.to_q
     RUN(f, lin_chain_launch(lc, f.st));
   } else {
     // ---- attn1.to_out + residual, norm2; cross-attention (P2P edits + store happen inside the kernel)
@@ -534,6 +553,20 @@ int transformer(Fwd& f, const Attn& a, const bf16_t* x, int H, int W, bf16_t** o
   }
   f.ar.free(ao);
   f.ar.free(t0);
+  *t1_out = t1;
+  *q2_out = q2;
+  return HEDIT_OK;
+}
+
+// transformer_rest: the cross-attention and the block tail on x (the block's input and last residual), t1 and q2, which
+// it frees; x [M][C] -> *out [M][C] (allocated here; x is NOT freed)
+int transformer_rest(Fwd& f, const Attn& a, const bf16_t* x, bf16_t* t1, bf16_t* q2, int H, int W, bf16_t** out,
+                     bf16_t* dst = nullptr, int ldd = 0) {
+  const int C = a.C, N = H * W, B = f.B, heads = f.h->cfg.heads, d = C / heads;
+  const size_t M = (size_t)B * N;
+  const hedit_p2p_plan* pl = (f.plan && f.plan->mode > 0) ? f.plan : nullptr;
+  bf16_t *tn, *ao, *k2, *vt2, *t2, *gf, *t3, *y;
+  const bool chain = a.ffs != nullptr;
   const int MC = B * HEDIT_CTXP;
   k2 = const_cast<bf16_t*>(f.k2_all) + a.ctx_off;                      // row stride ctx_n
   vt2 = const_cast<bf16_t*>(f.vt2_all) + (size_t)a.ctx_off * MC;
@@ -576,7 +609,7 @@ int transformer(Fwd& f, const Attn& a, const bf16_t* x, int H, int W, bf16_t** o
     fp.stream = a.ffs; fp.bias1p = a.ff1_bp; fp.bias2 = a.ff2_b; fp.out = y; fp.ldo = dst ? ldd : C; fp.M = (int)M; fp.C = C;
     {
       ProfScope ps(f, PK_LINEAR, 2.0 * M * 14.0 * C * C, 8.0 * M * C + 28.0 * C * C);      // a, t1, x read, out written; weights once
-      chain_prof(ps, 14, 128);                                                              // tag 128: the fused block tail
+      chain_prof(f, ps, M, C, 14, 128);                                                  // tag 128: the fused block tail
       RUN(f, ffn_fused_launch(fp, f.st));
     }
     f.ar.free(ao);
@@ -615,14 +648,58 @@ int transformer(Fwd& f, const Attn& a, const bf16_t* x, int H, int W, bf16_t** o
   return HEDIT_OK;
 }
 
-struct Skip { bf16_t* p; int C; };
+// x [M][C] -> *out [M][C] (allocated here; x is NOT freed)
+int transformer(Fwd& f, const Attn& a, const bf16_t* x, int H, int W, bf16_t** out, bf16_t* dst = nullptr, int ldd = 0) {
+  bf16_t *t1, *q2;
+  TRY(transformer_stem(f, a, x, H, W, &t1, &q2));
+  return transformer_rest(f, a, x, t1, q2, H, W, out, dst, ldd);
+}
 
+struct Skip { bf16_t* p; int C; bool per_latent = false; };   // per_latent: one image per distinct latent, read through the row map
+
+// May the part in front of the first cross-attention run once per distinct latent?  Only while nothing in it looks at
+// another row or hands a row's self-attention to the caller.  N0 = tokens of the first transformer block.
+bool stem_shareable(const hedit_unet* h, const hedit_p2p_plan* plan, int D, int B, int N0) {
+  if (D >= B || h->hook || h->down.empty() || !h->down[0].has_attn) return false;
+  const hedit_p2p_plan* pl = (plan && plan->mode > 0) ? plan : nullptr;
+  if (!pl) return true;
+  if (pl->feat_src && pl->feat_resblock <= 0) return false;
+  if (pl->kv_src && pl->kv_first_block <= 0) return false;
+  if (pl->qk_src && N0 <= (pl->qk_max_tokens > 0 ? pl->qk_max_tokens : 1024) && pl->qk_first_block <= 0) return false;
+  if (pl->mode == 2 && pl->h_store_self && pl->n_store_self > 0 && N0 <= 1024) return false;
+  return true;
+}
+
+// The block's input, t1 and q2 of the first transformer, computed per distinct latent, become per batch row: one launch
+int broadcast_stem(Fwd& f, size_t row_elems, bf16_t** x, bf16_t** t1, bf16_t** q2, int D) {
+  bf16_t** narrow[3] = {x, t1, q2};
+  bf16_t* wide[3];
+  const void* src[3];
+  void* dst[3];
+  for (int i = 0; i < 3; ++i) {
+    TRY(aalloc(f, &wide[i], (size_t)f.B * row_elems));
+    src[i] = *narrow[i];
+    dst[i] = wide[i];
+  }
+  {
+    ProfScope ps(f, PK_OTHER, 0.0, 3.0 * (D + f.B) * (double)row_elems * sizeof(bf16_t));
+    RUN(f, gather_rows_launch(src, dst, 3, f.B, (long)(row_elems * sizeof(bf16_t)), *f.map, f.st));
+  }
+  for (int i = 0; i < 3; ++i) {
+    f.ar.free(*narrow[i]);
+    *narrow[i] = wide[i];
+  }
+  return HEDIT_OK;
+}
+
+// D == 0: x holds one latent per batch row.  D > 0 (hedit_unet_forward_shared): x holds D distinct latents and row r
+// evaluates latent map->src[r]; a dry run takes the row COUNT only (map == nullptr).
 int forward_impl(hedit_unet* h, const float* x, float t, const float* ctx, int B, int H0, int W0,
                  const hedit_p2p_plan* plan, float* eps_out, void* ws, size_t ws_bytes, hipStream_t st,
-                 bool dry, size_t* peak) {
+                 bool dry, size_t* peak, int D = 0, const RowMap* map = nullptr) {
   const hedit_unet_cfg& c = h->cfg;
   Fwd f;
-  f.h = h; f.B = B; f.st = st; f.plan = plan;
+  f.h = h; f.B = B; f.st = st; f.plan = plan; f.map = map;
   f.ar.base = reinterpret_cast<char*>(ws); f.ar.cap = ws_bytes; f.ar.dry = dry;
   const int ch0 = c.block_out_channels[0];
 
@@ -662,26 +739,50 @@ int forward_impl(hedit_unet* h, const float* x, float t, const float* ctx, int B
   RUN(f, gemv_launch(h->temb_w_all, te2, h->temb_b_all, h->conv1_b_all, temb_all, h->temb_total, h->temb_dim, 1, st));
   f.temb_all = temb_all;
 
-  // ---- stem
+  // ---- stem.  With a row map: once per distinct latent where that is the same arithmetic (stem_shareable), else the
+  // latents are spread to one per row first and everything below is the plain path
   int H = H0, W = W0;
+  const bool share = D > 0 && stem_shareable(h, plan, D, B, H0 * W0);
+  float* xrows = nullptr;
+  if (D > 0 && !share) {
+    const size_t img = (size_t)c.in_channels * H * W;
+    TRY(aalloc(f, &xrows, (size_t)B * img));
+    const void* src[1] = {x};
+    void* dst[1] = {xrows};
+    ProfScope ps(f, PK_OTHER, 0.0, (double)(D + B) * img * sizeof(float));
+    RUN(f, gather_rows_launch(src, dst, 1, B, (long)(img * sizeof(float)), *map, st));
+    x = xrows;
+  }
   bf16_t* cur;
-  TRY(aalloc(f, &cur, (size_t)B * H * W * ch0));
-  RUN(f, conv_in_launch(x, h->conv_in_w, h->conv_in_b, cur, B, c.in_channels, H, W, ch0, st));
+  {
+    BatchScope rows(f, share ? D : B);
+    TRY(aalloc(f, &cur, (size_t)f.B * H * W * ch0));
+    RUN(f, conv_in_launch(x, h->conv_in_w, h->conv_in_b, cur, f.B, c.in_channels, H, W, ch0, st));
+  }
+  if (xrows) f.ar.free(xrows);
   std::vector<Skip> skips;
-  skips.push_back({cur, ch0});
+  skips.push_back({cur, ch0, share});      // the first skip stays per latent: its concatenation copies it anyway
 
   // ---- down path
   for (int i = 0; i < c.n_levels; ++i) {
     Block& blk = h->down[i];
     for (size_t j = 0; j < blk.res.size(); ++j) {
-      bf16_t* y;
-      TRY(resblock(f, blk.res[j], cur, H, W, &y));
+      const bool stem = share && i == 0 && j == 0;      // still per latent: up to the first cross-attention
+      bf16_t *y, *t1 = nullptr, *q2 = nullptr;
+      {
+        BatchScope rows(f, stem ? D : B);
+        TRY(resblock(f, blk.res[j], cur, H, W, &y));
+        if (blk.has_attn) {
+          f.place = 0;
+          TRY(transformer_stem(f, blk.attn[j], y, H, W, &t1, &q2));
+        }
+      }
       // cur stays alive as a skip
       cur = y;
+      if (stem) TRY(broadcast_stem(f, (size_t)H * W * blk.ch, &cur, &t1, &q2, D));
       if (blk.has_attn) {
         bf16_t* z;
-        f.place = 0;
-        TRY(transformer(f, blk.attn[j], cur, H, W, &z));
+        TRY(transformer_rest(f, blk.attn[j], cur, t1, q2, H, W, &z));
         f.ar.free(cur);
         cur = z;
       }
@@ -724,10 +825,10 @@ int forward_impl(hedit_unet* h, const float* x, float t, const float* ctx, int B
       const size_t M = (size_t)B * H * W;
       if (in_cat) {
         cat = cat_next;
-        { ProfScope ps(f, PK_OTHER, 0.0); RUN(f, concat_launch(nullptr, cur_c, s.p, s.C, cat, (long)M, st)); }
+        { ProfScope ps(f, PK_OTHER, 0.0); RUN(f, concat_launch(nullptr, cur_c, s.p, s.C, cat, (long)M, st, s.per_latent ? f.map : nullptr, H * W)); }
       } else {
         TRY(aalloc(f, &cat, M * (cur_c + s.C)));
-        { ProfScope ps(f, PK_OTHER, 0.0); RUN(f, concat_launch(cur, cur_c, s.p, s.C, cat, (long)M, st)); }
+        { ProfScope ps(f, PK_OTHER, 0.0); RUN(f, concat_launch(cur, cur_c, s.p, s.C, cat, (long)M, st, s.per_latent ? f.map : nullptr, H * W)); }
         f.ar.free(cur);
       }
       f.ar.free(s.p);
@@ -1002,16 +1103,27 @@ int hedit_unet_missing(const hedit_unet* h) try {
   return m;
 } catch (...) { return hedit_abi_catch(); }
 
+/* enough for hedit_unet_forward and for hedit_unet_forward_shared under ANY row map: the arena's layout depends on how many
+   rows the shared part runs at, so every count of distinct latents gets its dry run (D == B: the latents are spread to one
+   per row first, what a call that may not share does) */
 size_t hedit_unet_workspace_bytes(hedit_unet* h, int B, int height, int width) try {
   if (!h) return 0;
-  size_t peak = 0;
-  if (forward_impl(h, nullptr, 0.f, nullptr, B, height, width, nullptr, nullptr, nullptr, 0, nullptr, true, &peak) != HEDIT_OK) return 0;
-  return peak + 4096;
+  const std::array<int, 4> key{B, height, width, h->hook ? 1 : 0};
+  auto it = h->ws_cache.find(key);
+  if (it != h->ws_cache.end()) return it->second;
+  size_t need = 0;
+  for (int D = 0; D <= (B <= HEDIT_ROWMAP_MAX ? B : 0); ++D) {
+    size_t peak = 0;
+    if (forward_impl(h, nullptr, 0.f, nullptr, B, height, width, nullptr, nullptr, nullptr, 0, nullptr, true, &peak, D) != HEDIT_OK) return 0;
+    if (peak > need) need = peak;
+  }
+  need += 4096;
+  h->ws_cache[key] = need;
+  return need;
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
-int hedit_unet_forward(hedit_unet* h, const float* x, float t, const float* ctx, int B, int height, int width,
-                       const hedit_p2p_plan* plan, float* eps_out, void* workspace, size_t workspace_bytes,
-                       void* stream) try {
+static int forward_checks(hedit_unet* h, const float* x, const float* ctx, int B, int height, int width, const hedit_p2p_plan* plan,
+                          float* eps_out, void* workspace) {
   ARG_CHECK(h && x && ctx && eps_out && workspace, "null");
   ARG_CHECK(B >= 1, "B");
   const int div = 1 << (h->cfg.n_levels - 1);
@@ -1027,8 +1139,34 @@ int hedit_unet_forward(hedit_unet* h, const float* x, float t, const float* ctx,
     ARG_CHECK(plan->n_pairs >= 0 && plan->n_pairs + plan->n_single > 0, "plan rows");
     ARG_CHECK(plan->n_pairs == 0 || (plan->pair_src && plan->pair_tar && plan->mixT && plan->bvec), "plan tables");
   }
+  return HEDIT_OK;
+}
+
+int hedit_unet_forward(hedit_unet* h, const float* x, float t, const float* ctx, int B, int height, int width,
+                       const hedit_p2p_plan* plan, float* eps_out, void* workspace, size_t workspace_bytes,
+                       void* stream) try {
+  TRY(forward_checks(h, x, ctx, B, height, width, plan, eps_out, workspace));
   return forward_impl(h, x, t, ctx, B, height, width, plan, eps_out, workspace, workspace_bytes,
                       reinterpret_cast<hipStream_t>(stream), false, nullptr);
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_unet_forward_shared(hedit_unet* h, const float* x, int D, const int* row_latent, float t, const float* ctx, int B,
+                              int height, int width, const hedit_p2p_plan* plan, float* eps_out, void* workspace,
+                              size_t workspace_bytes, void* stream) try {
+  TRY(forward_checks(h, x, ctx, B, height, width, plan, eps_out, workspace));
+  ARG_CHECK(row_latent && D >= 1 && D <= 65535, "row map");
+  if (B > HEDIT_ROWMAP_MAX) {
+    hedit_set_error("batch larger than " + std::to_string(HEDIT_ROWMAP_MAX) + " rows (the row map of shared latents)");
+    return HEDIT_ERR_ARG;
+  }
+  ARG_CHECK(reinterpret_cast<uintptr_t>(x) % 16 == 0, "x must be 16-byte aligned");
+  RowMap map{};      // handed to the kernels by value: nothing to upload, nothing to keep alive
+  for (int r = 0; r < B; ++r) {
+    ARG_CHECK(row_latent[r] >= 0 && row_latent[r] < D, "row_latent entries must lie in [0, D)");
+    map.src[r] = (uint16_t)row_latent[r];
+  }
+  return forward_impl(h, x, t, ctx, B, height, width, plan, eps_out, workspace, workspace_bytes,
+                      reinterpret_cast<hipStream_t>(stream), false, nullptr, D, &map);
 } catch (...) { return hedit_abi_catch(); }
 
 int hedit_prof_enable(hedit_unet* h, int on, int max_records) try {

@@ -78,6 +78,8 @@ _SIGS = {
     "hedit_unet_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int,
                                      C.c_int, C.POINTER(P2PPlan), C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
+    "hedit_unet_forward_shared": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_void_p, C.c_int,
+                                            C.c_int, C.c_int, C.POINTER(P2PPlan), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hedit_unet_set_attn_hook": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hedit_unet_num_store_layers": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "hedit_unet_store_layer_info": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),

@@ -73,8 +73,12 @@ class Schedule:
 
 
 class HEditEngine:
-    def __init__(self, model):
+    def __init__(self, model, share_latents=True):
         self.model = model
+        # The sampler's UNet calls evaluate each latent under several contexts.  True: such a call hands the executor the
+        # distinct latents and a row map (UNet2DConditionModel.forward_raw(row_latent=)), which runs the context-free front
+        # of the network once per latent -- the same bits.  False: the rows are materialised with torch.cat first.
+        self.share_latents = share_latents
         self.unet = model.unet
         self.lib = _lib.lib()
         self.dev = model.unet.device
@@ -232,13 +236,22 @@ class HEditEngine:
         if step_cb is not None and not callable(step_cb):
             raise TypeError("controller.step_callback must be callable as step_callback(x_t) -> x_t")
 
-        def p2p_pass(x_in, t, save):
-            rows = x_in.shape[0]
+        share = self.share_latents
+
+        def unet_rows(parts, blocks, t, ctx_rows, plan=None):
+            """One UNet call on the rows torch.cat([parts[b] for b in blocks]); every part is n latents."""
+            if not share:
+                return self.unet.forward_raw(torch.cat([parts[b] for b in blocks]), t, ctx_rows, plan)
+            lat = parts[0] if len(parts) == 1 else torch.cat(parts)
+            return self.unet.forward_raw(lat, t, ctx_rows, plan, row_latent=[b * n + j for b in blocks for j in range(n)])
+
+        def p2p_pass(parts, blocks, t, save):
+            rows = len(blocks) * n
             if foreign:
-                return self.unet.forward_hooked(x_in, t, ctx_edit, controller, save)
+                return self.unet.forward_hooked(torch.cat([parts[b] for b in blocks]), t, ctx_edit, controller, save)
             # controller=None: the reference's processors then leave every attention map alone (ptp_utils.py:98-101)
-            plan = controller._plan(self.unet, rows, x_in.shape[2], x_in.shape[3], save) if controller is not None else None
-            e = self.unet.forward_raw(x_in, t, ctx_edit5 if rows == 5 * n else ctx_edit, plan)
+            plan = controller._plan(self.unet, rows, xT.shape[2], xT.shape[3], save) if controller is not None else None
+            e = unet_rows(parts, blocks, t, ctx_edit5 if rows == 5 * n else ctx_edit, plan)
             if controller is not None:
                 controller._after_pass(save)
             return e
@@ -255,7 +268,7 @@ class HEditEngine:
             if (not p2p) and implicit and i == 0 and ahead != -1:
                 # one extra correction of the start sample when steps were skipped (p2p_h_edit.py:239-267)
                 xe = xt[n:]
-                e = self.unet.forward_raw(torch.cat([xe] * 4), t, ctx_edit, off)
+                e = unet_rows([xe], (0, 0, 0, 0), t, ctx_edit, off)
                 c0 = S.step_coef(t, tt, eta_i, ddim_inv, cfg_scales, w_rec, coeff=S.edit_coeff(ahead, t, eta_i, ddim_inv))
                 new = torch.empty_like(xe)
                 self.step_update(e[0:n], e[2 * n:3 * n], e[n:2 * n], e[3 * n:], xe, xe, new, n, False, c0)
@@ -263,14 +276,14 @@ class HEditEngine:
 
             # ---- base pass -> x_{t-1}^orig, x_{t-1}^base
             if p2p and reuse and carry is not None:
-                e2 = self.unet.forward_raw(torch.cat([xt[n:], xt[n:]]), t, ctx_base2, off)
+                e2 = unet_rows([xt[n:]], (0, 0), t, ctx_base2, off)
                 e = torch.cat([carry[0], e2[:n], carry[1], e2[n:]])
                 self.step_base(e, xt, z, x_prev, n, 4, coef)
             elif p2p:
-                e = self.unet.forward_raw(torch.cat([xt, xt]), t, ctx_base4, off)
+                e = unet_rows([xt[:n], xt[n:]], (0, 1, 0, 1), t, ctx_base4, off)
                 self.step_base(e, xt, z, x_prev, n, 4, coef)
             else:
-                e = self.unet.forward_raw(torch.cat([xt[n:], xt[n:]]), t, ctx_base2, off)
+                e = unet_rows([xt[n:]], (0, 0), t, ctx_base2, off)
                 self.step_base(e, xt, z, x_prev, n, 2, coef)
             x_orig, x_base = x_prev[:n], x_prev[n:]
 
@@ -278,10 +291,10 @@ class HEditEngine:
                 new = torch.empty_like(x_base)
                 if p2p:
                     e_src = self.unet.forward_raw(xt[n:].contiguous(), t, ctx_src, off)
-                    e = p2p_pass(torch.cat([xt, xt]), t, True)
+                    e = p2p_pass([xt[:n], xt[n:]], (0, 1, 0, 1), t, True)
                     self.step_update(e[n:2 * n], e_src, e[n:2 * n], e[3 * n:], x_base, x_base, new, n, False, coef)
                 else:
-                    e = self.unet.forward_raw(torch.cat([xt[n:]] * 4), t, ctx_edit, off)
+                    e = unet_rows([xt[n:]], (0, 0, 0, 0), t, ctx_edit, off)
                     self.step_update(e[0:n], e[2 * n:3 * n], e[n:2 * n], e[3 * n:], x_base, x_base, new, n, False, coef)
                 x_k = new
             else:
@@ -291,11 +304,11 @@ class HEditEngine:
                     if p2p:
                         save = not (k < K - 1 and K > 1)
                         if fuse_src_pass:
-                            e = p2p_pass(torch.cat([x_orig, x_k, x_orig, x_k, x_k]), tt, save)
+                            e = p2p_pass([x_orig, x_k], (0, 1, 0, 1, 1), tt, save)
                             e_src = e[4 * n:]
                         else:
                             e_src = self.unet.forward_raw(x_k, tt, ctx_src, off)
-                            e = p2p_pass(torch.cat([x_orig, x_k, x_orig, x_k]), tt, save)
+                            e = p2p_pass([x_orig, x_k], (0, 1, 0, 1), tt, save)
                         self.step_update(e[n:2 * n], e_src, e[n:2 * n], e[3 * n:4 * n], x_k, x_base, new, n,
                                          k > 0 and style is None and rec_pull, coef)
                         if style is not None and style[0] is not None:
@@ -305,7 +318,7 @@ class HEditEngine:
                         if reuse:
                             carry = (e[0:n], e[2 * n:3 * n])
                     else:
-                        e = self.unet.forward_raw(torch.cat([x_k] * 4), tt, ctx_edit, off)
+                        e = unet_rows([x_k], (0, 0, 0, 0), tt, ctx_edit, off)
                         self.step_update(e[0:n], e[2 * n:3 * n], e[n:2 * n], e[3 * n:], x_k, x_base, new, n, k > 0, coef)
                     x_k = new
 
@@ -558,7 +571,10 @@ class HEditEngine:
             idx = T - i - 1
             xt = xts[idx + 1]
             if cond:
-                e = self.unet.forward_raw(torch.cat([xt, xt]), t, ctx)
+                if self.share_latents:
+                    e = self.unet.forward_raw(xt, t, ctx, row_latent=list(range(n)) * 2)
+                else:
+                    e = self.unet.forward_raw(torch.cat([xt, xt]), t, ctx)
                 e_u, e_c = e[:n], e[n:]
             else:
                 e_u = e_c = self.unet.forward_raw(xt.contiguous(), t, ctx)

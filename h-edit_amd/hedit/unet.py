@@ -261,9 +261,14 @@ class UNet2DConditionModel:
         return rows[:n.value]
 
     # ---------------------------------------------------------------- forward
-    def forward_raw(self, sample, t, ctx, plan=None, out=None):
-        """sample fp32 (B,C,H,W) cuda, t python float, ctx fp32 (B,77,D) cuda, plan: _lib.P2PPlan."""
+    def forward_raw(self, sample, t, ctx, plan=None, out=None, row_latent=None):
+        """sample fp32 (B,C,H,W) cuda, t python float, ctx fp32 (B,77,D) cuda, plan: _lib.P2PPlan.
+        row_latent (sequence of B ints): ``sample`` then holds only the DISTINCT latents and row r evaluates
+        ``sample[row_latent[r]]`` under ``ctx[r]`` -- the bits of the call on ``sample[row_latent]``, with the part of the
+        network in front of the first cross-attention run once per latent where the executor may (hedit_unet_forward_shared)."""
         B, Cc, H, W = sample.shape
+        if row_latent is not None:
+            B = len(row_latent)
         if sample.dtype != torch.float32 or ctx.dtype != torch.float32:
             raise TypeError("sample and encoder_hidden_states must be float32")
         if ctx.shape != (B, 77, self.config["cross_attention_dim"]):
@@ -274,8 +279,16 @@ class UNet2DConditionModel:
         if out is None:
             out = torch.empty(B, self.config["out_channels"], H, W, dtype=torch.float32, device=sample.device)
         ws = self._workspace(B, H, W)
-        _lib.check(self._lib.hedit_unet_forward(
-            self._h, _lib.ptr(sample), C.c_float(float(t)), _lib.ptr(ctx), B, H, W,
+        if row_latent is None:
+            _lib.check(self._lib.hedit_unet_forward(
+                self._h, _lib.ptr(sample), C.c_float(float(t)), _lib.ptr(ctx), B, H, W,
+                C.byref(plan) if plan is not None else None, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                _lib.cur_stream()))
+            return out
+        if sample.data_ptr() % 16:
+            sample = sample.clone()
+        _lib.check(self._lib.hedit_unet_forward_shared(
+            self._h, _lib.ptr(sample), sample.shape[0], (C.c_int * B)(*row_latent), C.c_float(float(t)), _lib.ptr(ctx), B, H, W,
             C.byref(plan) if plan is not None else None, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
             _lib.cur_stream()))
         return out

@@ -140,6 +140,17 @@ size_t hedit_unet_workspace_bytes(hedit_unet* h, int B, int height, int width);
 int hedit_unet_forward(hedit_unet* h, const float* x, float t, const float* ctx, int B, int height,
                        int width, const hedit_p2p_plan* plan, float* eps_out, void* workspace,
                        size_t workspace_bytes, void* stream);
+/* The same evaluation for a batch whose rows share latents -- classifier-free guidance and the h-Edit passes evaluate each
+ * latent under several contexts in one call.  x: fp32 [D][Cin][H][W], the D distinct latents (16-byte aligned);
+ * row_latent: HOST array of B ints in [0, D): row r evaluates x[row_latent[r]] under ctx[r].  ctx, plan, eps_out and the
+ * workspace are per row as above, and row r of eps_out has the bits hedit_unet_forward gives for that latent and context.
+ * What precedes the first cross-attention depends on the latent and t only, so it runs once per distinct latent whenever
+ * nothing there looks across rows: no hook, and no feature / key-value / query-key injection or self-map store of the plan
+ * that reaches the first block; otherwise the latents are spread to one per row first.  The map travels in the kernel
+ * arguments (nothing is uploaded, the host never waits); B <= 512.  hedit_unet_workspace_bytes(h, B, ..) covers any map. */
+int hedit_unet_forward_shared(hedit_unet* h, const float* x, int D, const int* row_latent, float t, const float* ctx, int B,
+                              int height, int width, const hedit_p2p_plan* plan, float* eps_out, void* workspace,
+                              size_t workspace_bytes, void* stream);
 /* Host-language attention controller -- the reference's hook point, text-guided/p2p/ptp_utils.py:98-106
  * (`self.controller(attention_probs, is_cross, self.place_in_unet, save_attn)` between the softmax and the product with V).
  * With a hook set, every attention layer of hedit_unet_forward writes its probabilities to HBM as fp32
