@@ -281,7 +281,8 @@ int local_blend_launch(const float* const* maps, int n_maps, int heads, const fl
 // ---------------------------------------------------------------- pnet.hip ("precise" fp32-quality building blocks)
 // ops of the fused element-wise stage that produces a split-bf16 GEMM operand (and of act_launch)
 enum { P_COPY = 0, P_AFFINE = 1, P_PRELU = 2, P_PRELU_GRAD = 3, P_RELU = 4, P_RELU_GRAD = 5, P_QGELU = 6, P_QGELU_GRAD = 7,
-       P_AFFINE_RELU = 8 };   // P_AFFINE_RELU: max(p x + q, 0), p / q per channel or per (image, channel) like P_AFFINE
+       P_AFFINE_RELU = 8,     // P_AFFINE_RELU: max(p x + q, 0), p / q per channel or per (image, channel) like P_AFFINE
+       P_GELU = 9 };          // P_GELU: the exact GELU 0.5 t (1 + erf(t / sqrt 2)) of t = x + q
 struct Split3Params {
   const float* x; int ldx;     // fp32 input rows [rows_in][ldx] (NHWC pixels x channels)
   const float* z;              // P_*_GRAD: the pre-activation the mask is taken from (same geometry as x)

@@ -65,6 +65,7 @@ __global__ __launch_bounds__(256) void split3_kernel(Split3Params s, long total)
             v = x * (sg * (1.0f + 1.702f * t * (1.0f - sg)));
             break;
           }
+          case P_GELU: { const float t = x + (s.q ? s.q[c] : 0.f); v = 0.5f * t * (1.0f + erff(t * 0.70710678118654752f)); break; }
           default: v = x;
         }
       }
@@ -138,6 +139,7 @@ __global__ __launch_bounds__(256) void split3_v8_kernel(Split3Params s, long tot
               y = v[e] * (sg * (1.0f + 1.702f * t * (1.0f - sg)));
               break;
             }
+            case P_GELU: { const float t = v[e] + qq[e]; y = 0.5f * t * (1.0f + erff(t * 0.70710678118654752f)); break; }
             default: y = v[e];
           }
           const bf16_t hi = bf16_rn(y);

@@ -15,11 +15,15 @@ when a LOCAL model is given with ``--clip_path`` (a transformers-style directory
 ``--clip_tokenizer DIR``) and ``--device cuda``; nothing is ever fetched.  ``lpips`` / ``lpips_unedit_part`` /
 ``lpips_edit_part`` (torchmetrics LPIPS with net_type='squeeze' on ``img * 2 - 1``, matrics_calculator.py:276,329-347) run
 on the native SqueezeNet-LPIPS (hedit/lpips_score.py, csrc/sqlpips.hip) when LOCAL weights are given with ``--lpips_path``
-(one state-dict file, or a directory holding the backbone file and the lin file) and ``--device cuda``.  The other network
-metrics need third-party checkpoints that do not exist offline and are not part of the sampling path (SURVEY.md section 8
-row f4 "then the evaluator"): ``local_clip`` (prompt templates + CLIP RN50 / ViT-B/32), ``structure_distance*`` (DINO
-ViT-B/8 self-similarity) -- asking for one of them, or for a CLIP score / LPIPS without its model, raises with the name of
-the missing checkpoint instead of writing a made-up number.
+(one state-dict file, or a directory holding the backbone file and the lin file) and ``--device cuda``.
+``structure_distance`` / ``structure_distance_unedit_part`` / ``structure_distance_edit_part`` (the mean squared difference
+of the DINO ViT-B/8 key self-similarity matrices, matrics_calculator.py:12-246,390-410) run on the native DINO key
+extractor (hedit/dino_score.py, csrc/dino.hip) when a LOCAL state dict is given with ``--dino_path`` (the published
+``dino_vitbase8_pretrain.pth``, or a directory holding exactly one ``.pth``) and ``--device cuda``.  The remaining network
+metric needs third-party checkpoints that do not exist offline and is not part of the sampling path (SURVEY.md section 8
+row f4 "then the evaluator"): ``local_clip`` (prompt templates + CLIP RN50 / ViT-B/32) -- asking for it, or for a CLIP
+score / LPIPS / structure distance without its model, raises with the name of the missing checkpoint instead of writing a
+made-up number.
 """
 import argparse
 import csv
@@ -32,7 +36,7 @@ import torch.nn.functional as F
 from PIL import Image
 
 PIXEL_METRICS = ("psnr", "mse", "ssim")
-NETWORK_METRICS = {"lpips": "torchmetrics LPIPS (SqueezeNet) weights", "structure_distance": "DINO ViT-B/8 weights",
+NETWORK_METRICS = {"lpips": "torchmetrics LPIPS (SqueezeNet) weights", "structure_distance": "DINO ViT-B/8 weights (a local state dict: --dino_path)",
                    "clip_similarity_source_image": "CLIP ViT-L/14 weights", "clip_similarity_target_image": "CLIP ViT-L/14 weights",
                    "clip_similarity_target_image_edit_part": "CLIP ViT-L/14 weights", "local_clip": "CLIP ViT-B/32 weights"}
 
@@ -79,16 +83,28 @@ def _require_cuda(device, what, who="the CLIP towers run"):
 class MetricsCalculator:
     """The pixel metrics and the CLIP score of the reference's MetricsCalculator (matrics_calculator.py:271-390), same method
     names.  `clip`: a CLIP scorer (hedit.clip_score.NativeClip); without one ``calculate_clip_similarity`` raises.  `lpips`:
-    an LPIPS scorer (hedit.lpips_score.NativeSqueezeLpips); without one ``calculate_lpips`` raises."""
+    an LPIPS scorer (hedit.lpips_score.NativeSqueezeLpips); without one ``calculate_lpips`` raises.  `dino`: a structure
+    scorer (hedit.dino_score.NativeDinoStructure); without one ``calculate_structure_distance`` raises."""
 
-    def __init__(self, device="cpu", clip=None, lpips=None):
+    def __init__(self, device="cpu", clip=None, lpips=None, dino=None):
         self.device = device
         self.clip = clip              # hedit.clip_score.NativeClip (or anything with score(uint8 H x W x 3 array, text)), or None
         self.lpips = lpips            # hedit.lpips_score.NativeSqueezeLpips (or anything with score(pred, gt, mask_pred, mask_gt)), or None
         if clip is not None:
             _require_cuda(device, "CLIP score")
+        self.dino = dino              # hedit.dino_score.NativeDinoStructure (or anything with score(pred, gt, mask_pred, mask_gt)), or None
         if lpips is not None:
             _require_cuda(device, "LPIPS", "SqueezeNet-LPIPS runs")
+        if dino is not None:
+            _require_cuda(device, "structure distance", "the DINO key extractor runs")
+
+    def calculate_structure_distance(self, img_pred, img_gt, mask_pred=None, mask_gt=None):
+        """matrics_calculator.py:390-410: both images as float32 in 0...255 (NOT / 255), times their masks, through the DINO
+        key self-similarity (the scorer does that preprocessing: the resize and the normalisation go with the network)"""
+        if self.dino is None:
+            raise NotImplementedError("structure_distance: needs " + NETWORK_METRICS["structure_distance"] + ", which this run does not have")
+        assert np.array(img_pred).shape == np.array(img_gt).shape, "Image shapes should be the same."
+        return float(self.dino.score(img_pred, img_gt, mask_pred, mask_gt))
 
     def calculate_lpips(self, img_pred, img_gt, mask_pred=None, mask_gt=None):
         """matrics_calculator.py:329-347: both images / 255, times their masks, * 2 - 1, through SqueezeNet-LPIPS (the
@@ -148,7 +164,8 @@ def calculate_metric(mc, metric, src_image, tgt_image, src_mask, tgt_mask, src_p
         if tgt_mask.sum() == 0:
             return "nan"
         return mc.calculate_clip_similarity(tgt_image, tgt_prompt, tgt_mask)
-    routed = PIXEL_METRICS + (("lpips",) if getattr(mc, "lpips", None) is not None else ())
+    routed = PIXEL_METRICS + (("lpips",) if getattr(mc, "lpips", None) is not None else ()) + \
+        (("structure_distance",) if getattr(mc, "dino", None) is not None else ())
     if (base in NETWORK_METRICS or metric in NETWORK_METRICS) and base not in routed:
         raise NotImplementedError(f"metric {metric}: needs {NETWORK_METRICS.get(base, NETWORK_METRICS.get(metric))}, which this offline "
                                   "build does not have; pixel metrics: " + ", ".join(PIXEL_METRICS))
@@ -184,6 +201,11 @@ def build_parser():
     p.add_argument('--lpips_path', type=str, default=None,
                    help="LOCAL SqueezeNet-LPIPS weights for the lpips* metrics: one state-dict file (lpips / torchmetrics spelling), or a "
                         "directory holding the backbone file (torchvision squeezenet1_1) and the lin file")
+    p.add_argument('--dino_path', type=str, default=None,
+                   help="LOCAL DINO ViT state dict for the structure_distance* metrics: the published dino_vitbase8_pretrain.pth, or a "
+                        "directory holding exactly one .pth")
+    p.add_argument('--dino_resolution', type=int, default=224,
+                   help="the side the DINO input is resized to; the checkpoint's pos_embed must fit it (no interpolation)")
     return p
 
 
@@ -206,9 +228,16 @@ def load_lpips(lpips_path, device):
     return NativeSqueezeLpips(lpips_path, device="cuda:0" if str(device) == "cuda" else device)
 
 
-def main(argv=None, clip=None, lpips=None):
-    """`clip` / `lpips`: ready scorers instead of --clip_path / --lpips_path (synthetic runs and tests:
-    NativeClip.from_standin, NativeSqueezeLpips())"""
+def load_dino(dino_path, device, resolution=224):
+    """The native DINO structure scorer of --dino_path on `device` (a local file only; torch.hub is never called)"""
+    _require_cuda(device, "--dino_path", "the DINO key extractor runs")
+    from hedit.dino_score import NativeDinoStructure
+    return NativeDinoStructure(dino_path, device="cuda:0" if str(device) == "cuda" else device, resolution=resolution)
+
+
+def main(argv=None, clip=None, lpips=None, dino=None):
+    """`clip` / `lpips` / `dino`: ready scorers instead of --clip_path / --lpips_path / --dino_path (synthetic runs and
+    tests: NativeClip.from_standin, NativeSqueezeLpips(), NativeDinoStructure())"""
     args = build_parser().parse_args(argv)
     if not args.tgt_folders or len(args.tgt_folders) != len(args.tgt_methods):
         raise SystemExit("give --tgt_folders DIR ... (one per method)")
@@ -217,7 +246,9 @@ def main(argv=None, clip=None, lpips=None):
         clip = load_clip(args.clip_path, args.clip_tokenizer, args.device)
     if lpips is None and args.lpips_path:
         lpips = load_lpips(args.lpips_path, args.device)
-    mc = MetricsCalculator(args.device, clip, lpips)
+    if dino is None and args.dino_path:
+        dino = load_dino(args.dino_path, args.device, args.dino_resolution)
+    mc = MetricsCalculator(args.device, clip, lpips, dino)
     os.makedirs(os.path.dirname(os.path.abspath(args.result_path)), exist_ok=True)
     with open(args.result_path, 'w', newline="") as f:
         csv.writer(f).writerow(["file_id"] + [f"{k}|{m}" for k in folders for m in args.metrics])
@@ -249,5 +280,5 @@ def main(argv=None, clip=None, lpips=None):
 
 if __name__ == "__main__":
     import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # the `hedit` package, for --clip_path / --lpips_path
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # the `hedit` package, for --clip_path / --lpips_path / --dino_path
     main()

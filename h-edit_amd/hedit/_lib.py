@@ -47,6 +47,10 @@ class ClipImgCfg(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("width", "layers", "heads", "patch_size", "input_resolution", "embed_dim")]
 
 
+class DinoCfg(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("width", "layers", "heads", "patch_size", "input_resolution", "key_layer")]
+
+
 class P2PPlan(C.Structure):
     _fields_ = [("mode", C.c_int), ("n_pairs", C.c_int),
                 ("pair_src", C.c_void_p), ("pair_tar", C.c_void_p),
@@ -202,6 +206,19 @@ _SIGS = {
     "hedit_sqlpips_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "hedit_sqlpips_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_size_t, C.c_void_p]),
+    "hedit_dino_create": (C.c_int, [C.POINTER(DinoCfg), C.POINTER(C.c_void_p)]),
+    "hedit_dino_destroy": (None, [C.c_void_p]),
+    "hedit_dino_num_params": (C.c_int, [C.c_void_p]),
+    "hedit_dino_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
+    "hedit_dino_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hedit_dino_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hedit_dino_missing": (C.c_int, [C.c_void_p]),
+    "hedit_dino_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "hedit_dino_set_slices": (C.c_int, [C.c_void_p, C.c_int]),
+    "hedit_dino_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    "hedit_dino_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hedit_dino_structure_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                C.c_void_p]),
     "hedit_vae_create": (C.c_int, [C.POINTER(VaeCfg), C.POINTER(C.c_void_p)]),
     "hedit_vae_destroy": (None, [C.c_void_p]),
     "hedit_vae_num_params": (C.c_int, [C.c_void_p]),

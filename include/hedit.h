@@ -641,6 +641,47 @@ int hedit_sqlpips_distance(hedit_sqlpips* h, const float* a, const float* b, int
                            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * DINO ViT key extractor and the key self-similarity distance, the `structure_distance*` columns of the PIE-Bench
+ * evaluator (text-guided/evaluation/matrics_calculator.py:12-246,390-410): the images, as 0..255 floats times their masks,
+ * are resized to input_resolution (bilinear, align_corners = False, no antialias), normalised with the ImageNet constants on
+ * the 0..255 values, and run through the public DINO ViT (conv patch embedding with bias, cls_token + pos_embed, pre-LN
+ * blocks with LayerNorm eps 1e-6, fused qkv, exact GELU) up to the keys of block `key_layer`; then S = K K^T /
+ * max(|k_i| |k_j|, 1e-8) and dist = mean((S_a - S_b)^2).  Forward only.  Blocks 0 .. key_layer - 1 run whole, block
+ * key_layer runs norm1 and the key third of qkv; nothing after that has a parameter slot.  fp32 stream, split-bf16
+ * linear layers with fp32 accumulation, attention and both Gram matrices on the exact fp32 matrix instruction with an
+ * order that is a function of the token count alone, no float atomics: dist[n] and keys[b] are bit-identical to the single
+ * calls, dist is symmetric in (a, b) bit for bit and exactly 0 for a = b, and both storage builds give the same bits.
+ * Parameters by the DINO state_dict names (`cls_token`, `pos_embed`, `patch_embed.proj.weight/.bias`,
+ * `blocks.{i}.norm1|norm2.*`, `blocks.{i}.attn.qkv|proj.*`, `blocks.{i}.mlp.fc1|fc2.*`), fp32 device tensors.
+ * width / heads = 64; (input_resolution / patch_size)^2 + 1 <= 1025 tokens. */
+#define HEDIT_DINO_MAX_PAIRS 64
+typedef struct hedit_dino hedit_dino;
+typedef struct { int width, layers, heads, patch_size, input_resolution, key_layer; } hedit_dino_cfg;
+/* HEDIT_ERR_ARG, before anything is allocated, for width / heads != 64, input_resolution % patch_size != 0, key_layer
+ * outside [0, layers), or more than 1025 tokens */
+int hedit_dino_create(const hedit_dino_cfg* cfg, hedit_dino** out);
+void hedit_dino_destroy(hedit_dino* h);
+int hedit_dino_num_params(const hedit_dino* h);
+const char* hedit_dino_param_name(const hedit_dino* h, int i);
+int hedit_dino_param_shape(const hedit_dino* h, int i, int* ndim, int* dims4);
+int hedit_dino_load(hedit_dino* h, const char* name, const float* dev_w, size_t numel, void* stream);
+int hedit_dino_missing(const hedit_dino* h);
+int hedit_dino_finalize(hedit_dino* h, void* stream);
+/* A TEST KNOB: slices > 0 sets the number of workgroups the query rows of one (image, head) are dealt to (clamped to the
+ * number of 128-row passes); 0, the default: one per pass.  The output bits do not depend on it. */
+int hedit_dino_set_slices(hedit_dino* h, int slices);
+/* bytes hedit_dino_structure_distance needs for N pairs of S x S images; enough for hedit_dino_keys of B <= 2 N images */
+size_t hedit_dino_workspace_bytes(hedit_dino* h, int N, int S);
+/* image fp32 [B][3][S][S] (device; 0..255, already times its mask) -> keys fp32 [B][L][W] of block key_layer, bias
+ * included.  HEDIT_ERR_STATE for a handle that is not finalized; HEDIT_ERR_ARG for B outside [1, 2 HEDIT_DINO_MAX_PAIRS],
+ * S outside [patch_size, 4096] or a workspace that is too small: all before anything is launched. */
+int hedit_dino_keys(hedit_dino* h, const float* image, int B, int S, float* keys, void* workspace, size_t workspace_bytes,
+                    void* stream);
+/* a, b fp32 [N][3][S][S] as above -> dist fp32 [N].  The same checks with N in [1, HEDIT_DINO_MAX_PAIRS]. */
+int hedit_dino_structure_distance(hedit_dino* h, const float* a, const float* b, int N, int S, float* dist, void* workspace,
+                                  size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Face-parsing network of the face-swapping task: `FaceParsing()` of face-swapping/arcface/face_parsing_model.py
  * (CelebAMask-HQ U-Net, feature_scale 4: filters 16/32/64/128/256, transposed-convolution up-sampling, BatchNorm,
  * 19 classes, argmax) as main_edit.py:120-127 / :184 runs it.  Parameters by the reference's state_dict names
