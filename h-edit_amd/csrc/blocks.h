@@ -30,8 +30,8 @@ struct VSlot {
   bool loaded;
   int ndim;
   int dims[4];
-  // input-gradient twin (decoder only), filled by the same hedit_vae_load call:
-  // 0 none, 1 bf16 [I][O], 2 bf16 [I][9][O] taps flipped, 3 fp32 IOHW taps flipped
+  // input-gradient twin (image decoder, pixel UNet with gradient), filled by the same load call:
+  // 0 none, 1 bf16 [I][O], 2 bf16 [I][9][O] taps flipped, 3 fp32 IOHW taps flipped, 4 bf16 [I][9][O] taps in place (stride-2 dgrad)
   int tkind = 0;
   void* tdst = nullptr;
 };
@@ -442,11 +442,12 @@ int attention(VF& f, const VAttn& a, const bf16_t* x, int H, int W, bf16_t** out
   return HEDIT_OK;
 }
 
+// any_width: channel counts whose C / 8 does not divide 256 (the pixel UNet's skip concatenations)
 int groupnorm_bwd(VF& f, const bf16_t* x, const bf16_t* dy, const bf16_t* add, bf16_t* dx, const float* g, const float* b,
-                  const float* stats, int HW, int C, int silu) {
+                  const float* stats, int HW, int C, int silu, bool any_width = false) {
   float* ws;
   TRY(aalloc(f, &ws, groupnorm_bwd_ws_bytes(f.B, HW, C) / sizeof(float)));
-  RUN(f, groupnorm_bwd_launch(x, dy, add, dx, g, b, stats, f.B, HW, C, f.groups, silu, ws, f.st));
+  RUN(f, groupnorm_bwd_launch(x, dy, add, dx, g, b, stats, f.B, HW, C, f.groups, silu, ws, f.st, any_width));
   f.ar.free(ws);
   return HEDIT_OK;
 }
@@ -472,7 +473,7 @@ int resblock_bwd(VF& f, const ResRec& rec, const bf16_t* dy, bf16_t** dx_out) {
     add = dsc;
   }
   TRY(aalloc(f, &dx, M * r.cin));
-  TRY(groupnorm_bwd(f, rec.x, da1, add, dx, r.n1g, r.n1b, rec.st1, H * W, r.cin, 1));
+  TRY(groupnorm_bwd(f, rec.x, da1, add, dx, r.n1g, r.n1b, rec.st1, H * W, r.cin, 1, true));   // cin: may be a concatenation
   f.ar.free(da1);
   if (dsc) f.ar.free(dsc);
   *dx_out = dx;
@@ -571,6 +572,8 @@ inline int store_load(ParamStore* h, const char* what, const char* name, const f
     TRY(pack_conv3x3_dgrad_launch(w, reinterpret_cast<bf16_t*>(s.tdst), s.O, s.I, st));
   } else if (s.tkind == 3) {
     TRY(flip_oihw_launch(w, reinterpret_cast<float*>(s.tdst), s.O, s.I, s.dims[2], st));
+  } else if (s.tkind == 4) {
+    TRY(pack_conv3x3_s2_dgrad_launch(w, reinterpret_cast<bf16_t*>(s.tdst), s.O, s.I, st));
   }
   s.loaded = true;
   return HEDIT_OK;

@@ -458,6 +458,23 @@ int hedit_k_pack_conv3x3_dgrad(const float* w, void* out, int O, int I, void* st
   return pack_conv3x3_dgrad_launch(w, reinterpret_cast<bf16_t*>(out), O, I, S(stream));
 } catch (...) { return hedit_abi_catch(); }
 
+int hedit_k_pack_conv3x3_s2_dgrad(const float* w, void* out, int O, int I, void* stream) try {
+  ARG_CHECK(w && out, "pack args");
+  return pack_conv3x3_s2_dgrad_launch(w, reinterpret_cast<bf16_t*>(out), O, I, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_conv3x3_s2_dgrad(const void* dy, const void* w_packed, void* dx, int B, int Hin, int Win, int O, int I, void* stream) try {
+  ARG_CHECK(dy && w_packed && dx, "conv3x3_s2_dgrad args");
+  return conv3x3_s2_dgrad_launch(reinterpret_cast<const bf16_t*>(dy), reinterpret_cast<const bf16_t*>(w_packed),
+                                 reinterpret_cast<bf16_t*>(dx), B, Hin, Win, O, I, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_slice_add(const void* src, int ld, int off, int c, void* dst, int64_t rows, int accumulate, void* stream) try {
+  ARG_CHECK(src && dst && rows >= 0, "slice_add args");
+  return slice_add_launch(reinterpret_cast<const bf16_t*>(src), ld, off, c, reinterpret_cast<bf16_t*>(dst), (long)rows, accumulate,
+                          S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
 int hedit_k_pack_linear_t(const float* w, void* out, int O, int I, void* stream) try {
   ARG_CHECK(w && out, "pack args");
   return pack_linear_t_launch(w, reinterpret_cast<bf16_t*>(out), O, I, S(stream));

@@ -285,8 +285,10 @@ size_t groupnorm_bwd_ws_bytes(int B, int HW, int C) {
 
 int groupnorm_bwd_launch(const bf16_t* x, const bf16_t* dy, const bf16_t* add, bf16_t* dx, const float* gamma,
                          const float* beta, const float* stats, int B, int HW, int C, int G, int silu, float* ws,
-                         hipStream_t st) {
-  ARG_CHECK(C % 8 == 0 && C % G == 0 && G <= 64 && C / 8 <= 256 && 256 % (C / 8) == 0,
+                         hipStream_t st, bool any_width) {
+  // any_width: C / 8 need not divide the block -- the kernels then run R = 256 / (C / 8) pixel rows per pass and leave the
+  // last 256 - R * C / 8 threads idle (every stage guards r < R): the skip concatenations of the pixel UNet (C = 192, 384, 768)
+  ARG_CHECK(C % 8 == 0 && C % G == 0 && G <= 64 && C / 8 <= 256 && (any_width || 256 % (C / 8) == 0),
             "groupnorm_bwd: C % 8, C % G, G <= 64, C/8 a divisor of 256");
   const int nslab = gb_nslab(B, HW, C);
   float* part = ws;

@@ -182,7 +182,7 @@ int pack_geglu_rows_launch(const float* w, bf16_t* out_bf16, float* out_f32, int
 size_t groupnorm_bwd_ws_bytes(int B, int HW, int C);
 int groupnorm_bwd_launch(const bf16_t* x, const bf16_t* dy, const bf16_t* add, bf16_t* dx, const float* gamma,
                          const float* beta, const float* stats, int B, int HW, int C, int G, int silu, float* ws,
-                         hipStream_t st);
+                         hipStream_t st, bool any_width = false);   // any_width: C / 8 <= 256 need not divide 256
 // ds = scale * p * (dp - rowsum(dp * p))
 int softmax_bwd_launch(const bf16_t* p, const float* dp, bf16_t* ds, long rows, int N, float scale, hipStream_t st);
 int transpose_bf16_launch(const bf16_t* src, bf16_t* dst, int R, int C, hipStream_t st);   // [R][C] -> [C][R]
@@ -193,6 +193,15 @@ int sum2x2_launch(const bf16_t* du, bf16_t* dx, int B, int H, int W, int C, hipS
 int pack_conv3x3_dgrad_launch(const float* w_oihw, bf16_t* out, int O, int I, hipStream_t st);
 int pack_linear_t_launch(const float* w, bf16_t* out, int O, int I, hipStream_t st);
 int flip_oihw_launch(const float* w, float* out, int O, int I, int k, hipStream_t st);
+
+// ---------------------------------------------------------------- s2dgrad.hip (pixel UNet input-gradient pieces)
+// dx [B][Hin][Win][I] = input gradient of the stride-2 3x3 conv with pad (0,1,0,1) applied to dy [B][Hin/2][Win/2][O];
+// wt = bf16 [I][9][O] from pack_conv3x3_s2_dgrad_launch (taps in place).  O % 64 == 0, I % 64 == 0, Hin and Win even.
+int conv3x3_s2_dgrad_launch(const bf16_t* dy, const bf16_t* wt, bf16_t* dx, int B, int Hin, int Win, int O, int I, hipStream_t st);
+int pack_conv3x3_s2_dgrad_launch(const float* w_oihw, bf16_t* out, int O, int I, hipStream_t st);
+// dst [rows][c] = src [rows][ld] columns [off, off + c) (accumulate = 0), or dst = round(fp32(dst) + fp32(src columns));
+// c, off, ld multiples of 8.  Backward of the skip concatenation.
+int slice_add_launch(const bf16_t* src, int ld, int off, int c, bf16_t* dst, long rows, int accumulate, hipStream_t st);
 
 // ---------------------------------------------------------------- attn.hip
 struct SelfAttnParams {

@@ -121,6 +121,14 @@ _SIGS = {
     "hedit_ddpm_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "hedit_ddpm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
+    "hedit_ddpm_create_grad": (C.c_int, [C.POINTER(DdpmCfg), C.POINTER(C.c_void_p)]),
+    "hedit_ddpm_grad_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    "hedit_ddpm_forward_keep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
+                                          C.c_void_p]),
+    "hedit_ddpm_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hedit_ddpm_release": (None, [C.c_void_p]),
+    "hedit_ddpm_vjp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_size_t, C.c_void_p]),
     "hedit_irse50_create": (C.c_int, [C.POINTER(C.c_void_p)]),
     "hedit_irse50_destroy": (None, [C.c_void_p]),
     "hedit_irse50_num_params": (C.c_int, [C.c_void_p]),
@@ -298,6 +306,10 @@ _SIGS = {
     "hedit_k_transpose": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "hedit_k_sum2x2": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "hedit_k_pack_conv3x3_dgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "hedit_k_pack_conv3x3_s2_dgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "hedit_k_conv3x3_s2_dgrad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_void_p]),
+    "hedit_k_slice_add": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "hedit_k_pack_linear_t": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "hedit_k_flip_oihw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
 }

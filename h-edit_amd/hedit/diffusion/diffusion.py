@@ -3,7 +3,12 @@ of the reference's ``face-swapping/diffusion/diffusion.py::Model`` (:192-341): c
 same config keys, called as ``model(x, t)`` with ``x`` (n, 3, S, S) and ``t`` the (n,) float tensor of
 equal timesteps the reference passes (h_edit_R.py:70-71; a scalar works too) -> eps (n, 3, S, S) fp32;
 attributes ``in_channels`` / ``resolution`` read by the SDE inversion (sde_inversion.py:32-33);
-state_dict key names of the reference class.  GPU only -- there is no eager path."""
+state_dict key names of the reference class.  GPU only -- there is no eager path.
+
+``Model(config, device, grad=True)`` also carries the input-gradient weights (hedit_ddpm_create_grad): whenever grad
+mode is on and ``x.requires_grad`` the call is an autograd node whose backward is the executor's input-gradient pass
+(what the face task's Edit Friendly mode differentiates, face-swapping/inversion/ef.py:64-66,95,106).  Weights and ``t``
+take no gradient."""
 import ctypes as C
 
 import torch
@@ -20,12 +25,37 @@ TINY_DDPM_CONFIG = dict(type="simple", in_channels=3, out_ch=3, ch=64, ch_mult=(
                         num_diffusion_timesteps=1000)
 
 
+class _EpsGrad(torch.autograd.Function):
+    """eps = model(x, t) with the forward's tape kept in the model's workspace; backward = the executor's vector-Jacobian
+    product.  The tape stays until the model's next call, so ``retain_graph=True`` and a second backward work (ef.py:95,
+    :106); a backward after the model has run again is an error, not a wrong gradient."""
+
+    @staticmethod
+    def forward(ctx, x, model, t0):
+        ctx.model = model
+        ctx.ticket, eps = model._keep(x.detach(), t0)
+        ctx.shape = x.shape
+        return eps
+
+    @staticmethod
+    def backward(ctx, g):
+        m = ctx.model
+        if m._ticket != ctx.ticket:
+            raise RuntimeError("hedit.diffusion.Model: the kept forward of this graph was dropped by a later model call")
+        g = g.detach().to(dtype=torch.float32).contiguous()
+        dx = torch.empty(ctx.shape, dtype=torch.float32, device=m.device)
+        with torch.cuda.device(m.device):
+            _lib.check(m._lib.hedit_ddpm_backward(m._h, _lib.ptr(g), _lib.ptr(dx), _lib.ptr(m._ws), _lib.cur_stream()))
+        return dx, None, None
+
+
 class Model:
     # the timestep is a launch parameter: a (n,) tensor that still lives on the host is read without a device
     # synchronisation, so callers that know t on the host (the loops do) should not move it to the GPU first
     accepts_host_timesteps = True
+    _tickets = 0      # kept forwards so far, over all models: a ticket is never reused
 
-    def __init__(self, config=None, device="cuda:0"):
+    def __init__(self, config=None, device="cuda:0", grad=False):
         cfg = dict(CELEBA_HQ_CONFIG)
         cfg.update(config or {})
         if not cfg.get("resamp_with_conv", True):
@@ -53,8 +83,11 @@ class Model:
         c.num_res_blocks, c.image_size = cfg["num_res_blocks"], cfg["image_size"]
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.hedit_ddpm_create(C.byref(c), C.byref(h)))
+            create = self._lib.hedit_ddpm_create_grad if grad else self._lib.hedit_ddpm_create
+            _lib.check(create(C.byref(c), C.byref(h)))
         self._h = h
+        self.grad = bool(grad)
+        self._ticket = 0          # identifies the kept forward; 0 = none
         self.param_shapes = {}
         nd, dims = C.c_int(), (C.c_int * 4)()
         for i in range(self._lib.hedit_ddpm_num_params(self._h)):
@@ -110,9 +143,18 @@ class Model:
     def __call__(self, x, t):
         return self.forward(x, t)
 
-    @torch.no_grad()
     def forward(self, x, t):
         assert x.shape[2] == x.shape[3] == self.resolution
+        t0 = self._timestep(t)
+        if self.grad:
+            self._release()
+            if torch.is_grad_enabled() and torch.is_tensor(x) and x.requires_grad:
+                return _EpsGrad.apply(x.to(device=self.device, dtype=torch.float32), self, t0)
+        with torch.no_grad():
+            return self._forward(x, t0)
+
+    @staticmethod
+    def _timestep(t):
         if torch.is_tensor(t):
             tv = t.detach().float().reshape(-1)
             t0 = float(tv[0])
@@ -120,14 +162,37 @@ class Model:
                 raise NotImplementedError("one timestep per call (the reference passes ones(n) * t)")
         else:
             t0 = float(t)
-        x = x.detach().to(device=self.device, dtype=torch.float32).contiguous()
-        B = x.shape[0]
-        need = self._lib.hedit_ddpm_workspace_bytes(self._h, B)
+        return t0
+
+    def _workspace(self, need, what):
         if need == 0:
-            raise RuntimeError("hedit_ddpm_workspace_bytes failed: " + self._lib.hedit_last_error().decode())
+            raise RuntimeError(what + " failed: " + self._lib.hedit_last_error().decode())
         if self._ws is None or self._ws.numel() < need:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+
+    def _release(self):
+        if self._ticket:
+            self._lib.hedit_ddpm_release(self._h)
+            self._ticket = 0
+
+    def _keep(self, x, t0):
+        """forward that leaves its tape in the workspace -> (the ticket a backward must present, eps)"""
+        x = x.contiguous()
+        B = x.shape[0]
+        self._workspace(self._lib.hedit_ddpm_grad_workspace_bytes(self._h, B), "hedit_ddpm_grad_workspace_bytes")
+        eps = torch.empty(B, self.config["out_ch"], self.resolution, self.resolution, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.hedit_ddpm_forward_keep(self._h, _lib.ptr(x), t0, B, _lib.ptr(eps), _lib.ptr(self._ws),
+                                                         self._ws.numel(), _lib.cur_stream()))
+        Model._tickets += 1
+        self._ticket = Model._tickets
+        return self._ticket, eps
+
+    def _forward(self, x, t0):
+        x = x.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        B = x.shape[0]
+        self._workspace(self._lib.hedit_ddpm_workspace_bytes(self._h, B), "hedit_ddpm_workspace_bytes")
         out = torch.empty(B, self.config["out_ch"], self.resolution, self.resolution, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.hedit_ddpm_forward(self._h, _lib.ptr(x), t0, B, _lib.ptr(out), _lib.ptr(self._ws),

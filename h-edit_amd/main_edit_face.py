@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Face-swapping driver on the HIP path: same flags, dataset format (``--json_file``: a list of ``{idx, source, ref}``)
 and output naming as the reference's ``face-swapping/main_edit.py`` (:35-60 flags, :134-224 loop) for its h-Edit mode
-(``h_edit_R``): pixel DDPM UNet on the HIP executor, SDE inversion, h_Edit_R with the ArcFace identity reward.
+(``h_edit_R``): pixel DDPM UNet on the HIP executor, SDE inversion, h_Edit_R with the ArcFace identity reward.  Its comparison
+mode (``ef``, Edit Friendly: main_edit.py:201-204, inversion/ef.py) runs through ``main_edit_face_ef.py``, which calls ``main``
+here with ``modes=("ef",)``: like the text drivers (main_baselines.py), the h-Edit driver itself refuses the comparison modes.
+``ef`` differentiates the rewards through the eps-network, so it builds the UNet with its input-gradient pass (``Model(grad=True)``).
 
 Differences, all additive:
   * ``--ddpm_ckpt`` / ``--arcface_ckpt``: LOCAL checkpoint files (the reference hard-codes ./diffusion/weights/celeba_hq.ckpt
@@ -14,7 +17,7 @@ Differences, all additive:
     ``--mask_dir DIR`` with label images ``<source stem>.png`` (face-parsing class ids) takes precedence over the
     network; with neither, the result is saved unblended.  The cosine similarity is printed for the blended image.
   * under torch.distributed.run the pairs are sharded over the ranks (one process per GPU).
-The ``ef`` baseline mode is refused."""
+Any mode outside ``modes`` is refused."""
 import argparse
 import json
 import os
@@ -31,6 +34,7 @@ from hedit import dist as D  # noqa: E402
 from hedit.arcface import FaceParsing, IDLoss, face_mask  # noqa: E402
 from hedit.arcface.arcface_model import load_face_image  # noqa: E402
 from hedit.diffusion import Model, TINY_DDPM_CONFIG  # noqa: E402
+from hedit.inversion.ef_face import ef  # noqa: E402
 from hedit.inversion.h_edit_R import h_Edit_R  # noqa: E402
 from hedit.inversion.sde_inversion import inversion_forward_process_sde  # noqa: E402
 from hedit.utils import image_grid  # noqa: E402
@@ -48,7 +52,7 @@ def build_parser():
     p.add_argument("--json_file", type=str, default="./assets/demo/demo.json")
     p.add_argument("--image_path", type=str, default="./assets/demo/")
     p.add_argument('--output_path', type=str, default="./results/demo/")
-    p.add_argument("--mode", default="h_edit_R", help="modes: h_edit_R")
+    p.add_argument("--mode", default="h_edit_R", help="modes: h_edit_R (ef: main_edit_face_ef.py)")
     p.add_argument("--num_diffusion_steps", type=int, default=100)
     p.add_argument("--skip", type=int, default=0)
     p.add_argument("--eta", type=float, default=1.0)
@@ -106,20 +110,22 @@ def linear_betas(device):
     return torch.from_numpy(np.linspace(0.0001, 0.02, 1000, dtype=np.float64)).float().to(device)
 
 
-def main(argv=None):
+def main(argv=None, modes=("h_edit_R",)):
+    """modes: what this entry runs -- ("h_edit_R",) for this driver, ("ef",) from main_edit_face_ef.py"""
     args = build_parser().parse_args(argv)
     assert args.eta == 1.0, "eta should be set to 1.0 for this experiment"
-    if args.mode != "h_edit_R":
-        raise NotImplementedError(f"mode {args.mode}: only h_edit_R is built")
+    if args.mode not in modes or args.mode not in ("h_edit_R", "ef"):
+        raise NotImplementedError(f"mode {args.mode}: this driver runs {', '.join(modes)} (ef: main_edit_face_ef.py)")
+    grad = args.mode == "ef"          # Edit Friendly differentiates through the eps-network
     rank, world, local_rank = D.env_rank_world()
     device = f"cuda:{local_rank if world > 1 else args.device_num}"
     torch.cuda.set_device(device)
     D.init_from_env(device)      # several ranks: RCCL group; rank 0 reads the checkpoints and broadcasts them
     if args.random_init:
-        model = Model(TINY_DDPM_CONFIG if args.tiny else None, device=device)
+        model = Model(TINY_DDPM_CONFIG if args.tiny else None, device=device, grad=grad)
         model.init_random(args.seed)
     elif args.ddpm_ckpt:
-        model = Model(device=device)
+        model = Model(device=device, grad=grad)
 
         def read_ddpm():
             states = torch.load(args.ddpm_ckpt, map_location="cpu")
@@ -138,6 +144,16 @@ def main(argv=None):
     if have_lpips and not args.random_init and not args.lpips_ckpt:
         raise SystemExit("give --lpips_ckpt FILE (saved lpips.LPIPS(net='vgg').state_dict()), or --no_lpips")
     face_parser = load_face_parser(args, device)
+
+    def edit(xT, zs, lpipsloss, idloss, after_skip_steps, per_image):
+        if args.mode == "ef":                            # main_edit.py:201-204
+            return ef(model, lpipsloss, idloss, xT, betas, seq, eta=args.eta, zs=zs, weight_edit_face=args.weight_edit_face,
+                      after_skip_steps=after_skip_steps, num_inference_steps=args.num_diffusion_steps, soft_face_mask=None,
+                      per_image=per_image)
+        return h_Edit_R(model, lpipsloss, idloss, xT, betas, seq, eta=args.eta, zs=zs, weight_edit_face=args.weight_edit_face,
+                        optimization_steps=args.optimization_steps, after_skip_steps=after_skip_steps,
+                        num_inference_steps=args.num_diffusion_steps, soft_face_mask=None, per_image=per_image)
+
     pairs = list(get_source_ref_paths(args.json_file))
     written = []
     mine = D.shard(len(pairs), rank, world)
@@ -164,10 +180,7 @@ def main(argv=None):
                                                               num_inference_steps=args.num_diffusion_steps, device=device)
                 zs_l.append(zs[:after_skip_steps])
                 xs_l.append(xts[after_skip_steps])
-            edited = h_Edit_R(model, lpipsloss, idloss, torch.stack(xs_l), betas, seq, eta=args.eta, zs=torch.stack(zs_l, 1),
-                              weight_edit_face=args.weight_edit_face, optimization_steps=args.optimization_steps,
-                              after_skip_steps=after_skip_steps, num_inference_steps=args.num_diffusion_steps, soft_face_mask=None,
-                              per_image=True).detach()
+            edited = edit(torch.stack(xs_l), torch.stack(zs_l, 1), lpipsloss, idloss, after_skip_steps, True).detach()
             masks = source_masks(args, face_parser, [sp for _, sp, _ in grp], torch.cat(srcs), S)
             if args.post_processing and masks is not None:
                 edited = torch.cat([edited[k:k + 1] * masks[k:k + 1] + srcs[k] * (1 - masks[k:k + 1]) for k in range(len(grp))])
@@ -196,9 +209,7 @@ def main(argv=None):
                                                        num_inference_steps=args.num_diffusion_steps, device=device)
         soft_face_mask = source_masks(args, face_parser, [source_path], source, S)
         after_skip_steps = args.num_diffusion_steps - args.skip
-        edited = h_Edit_R(model, lpipsloss, idloss, xts[after_skip_steps], betas, seq, eta=args.eta, zs=zs[:after_skip_steps],
-                          weight_edit_face=args.weight_edit_face, optimization_steps=args.optimization_steps,
-                          after_skip_steps=after_skip_steps, num_inference_steps=args.num_diffusion_steps, soft_face_mask=None)
+        edited = edit(xts[after_skip_steps], zs[:after_skip_steps], lpipsloss, idloss, after_skip_steps, False)
         x0_dec = edited.detach()
         if args.post_processing and soft_face_mask is not None:
             x0_dec = x0_dec * soft_face_mask + source * (1 - soft_face_mask)

@@ -442,6 +442,16 @@ int hedit_k_sum2x2(const void* du, void* dx, int B, int H, int W, int C, void* s
 int hedit_k_pack_conv3x3_dgrad(const float* w_oihw, void* out, int O, int I, void* stream);
 int hedit_k_pack_linear_t(const float* w, void* out, int O, int I, void* stream);
 int hedit_k_flip_oihw(const float* w_oihw, float* out, int O, int I, int k, void* stream);
+/* The two pieces the pixel UNet's input-gradient pass adds to those (csrc/s2dgrad.hip; tests/test_gpu_ddpm_grad.py).
+ * hedit_k_conv3x3_s2_dgrad: dx [B][Hin][Win][I] = the input gradient of the stride-2 3x3 convolution with padding (0,1,0,1)
+ *   (hedit_k_gemm mode 2 with asym; Hout = Hin / 2) applied to dy [B][Hin/2][Win/2][O].  Four sub-convolutions by the parity
+ *   of the dx pixel (4 / 2 / 2 / 1 taps), one fp32 MFMA chain per element in an order fixed by the layer's shape.  w_packed =
+ *   hedit_k_pack_conv3x3_s2_dgrad of the OIHW fp32 weight: bf16 [I][9][O], taps in place.  O % 64 == 0, I % 64 == 0, Hin, Win even.
+ * hedit_k_slice_add: dst [rows][c] = src [rows][ld] columns [off, off + c) (accumulate == 0), or dst = the fp32 sum of dst
+ *   and those columns rounded once (accumulate != 0): backward of the skip concatenation.  c, off, ld multiples of 8. */
+int hedit_k_pack_conv3x3_s2_dgrad(const float* w_oihw, void* out, int O, int I, void* stream);
+int hedit_k_conv3x3_s2_dgrad(const void* dy, const void* w_packed, void* dx, int B, int Hin, int Win, int O, int I, void* stream);
+int hedit_k_slice_add(const void* src, int ld, int off, int c, void* dst, int64_t rows, int accumulate, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Pixel-space DDPM UNet of the face-swapping task: `Model.forward(x, t)` of
@@ -469,6 +479,28 @@ size_t hedit_ddpm_workspace_bytes(hedit_ddpm* h, int B);
  * -> eps fp32 [B][out_ch][S][S] */
 int hedit_ddpm_forward(hedit_ddpm* h, const float* x, float t, int B, float* eps, void* workspace,
                        size_t workspace_bytes, void* stream);
+/* Input gradient of the eps-network: d_x = (d eps / d x)^T d_eps, what `torch.autograd.grad(loss, xt)` pulls through
+ * `model(xt, t)` in the face task's Edit Friendly mode (face-swapping/inversion/ef.py:64-66,95,106).  No weight gradient,
+ * none w.r.t. t.
+ * hedit_ddpm_create_grad = hedit_ddpm_create with the input-gradient weight twins attached (about as much device memory
+ *   again; filled by the same hedit_ddpm_load calls).  Every entry above works on such a handle unchanged.
+ * hedit_ddpm_forward_keep = hedit_ddpm_forward that leaves its tape (block inputs, conv1 outputs, GroupNorm statistics,
+ *   attention q / k) in the workspace, sized with hedit_ddpm_grad_workspace_bytes.  The taped forward takes every
+ *   GroupNorm's statistics itself, so where hedit_ddpm_forward takes them from the producing convolution (H*W >= 1024 and
+ *   C % 128 == 0) eps can differ from it in the last bits; elsewhere the bits are equal.
+ * hedit_ddpm_backward: d_eps [B][out_ch][S][S] -> d_x [B][in_channels][S][S], any number of times on one kept forward
+ *   (ef.py:95 retain_graph=True, :106); the same cotangent gives the same bits.  One outstanding forward per handle: the
+ *   next forward_keep, hedit_ddpm_release or hedit_ddpm_destroy drops the tape; the workspace must not be written in between.
+ * hedit_ddpm_vjp: forward_keep + one backward + release in one call, the same bits.
+ * A batch's rows are the bits of single calls, as everywhere. */
+int hedit_ddpm_create_grad(const hedit_ddpm_cfg* cfg, hedit_ddpm** out);
+size_t hedit_ddpm_grad_workspace_bytes(hedit_ddpm* h, int B);
+int hedit_ddpm_forward_keep(hedit_ddpm* h, const float* x, float t, int B, float* eps, void* workspace,
+                            size_t workspace_bytes, void* stream);
+int hedit_ddpm_backward(hedit_ddpm* h, const float* d_eps, float* d_x, void* workspace, void* stream);
+void hedit_ddpm_release(hedit_ddpm* h);
+int hedit_ddpm_vjp(hedit_ddpm* h, const float* x, float t, const float* d_eps, int B, float* d_x, float* eps, void* workspace,
+                   size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Identity reward of the face-swapping task: `IDLoss.get_cosine_loss(image)` of face-swapping/arcface/
