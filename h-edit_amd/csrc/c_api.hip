@@ -475,6 +475,69 @@ int hedit_k_slice_add(const void* src, int ld, int off, int c, void* dst, int64_
                           S(stream));
 } catch (...) { return hedit_abi_catch(); }
 
+// ---- the pieces of the SD UNet's input-gradient pass (attnbwd.hip, grad.hip, s2dgrad.hip)
+size_t hedit_k_attn_bwd_ws_bytes(int B, int N, int heads) { return attn_bwd_ws_bytes(B, N, heads); }
+
+static AttnBwdParams attn_bwd_params(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o, int ldo,
+                                     const void* dout, int lddo, void* dq, int lddq, int B, int N, int heads, int d) {
+  AttnBwdParams p{};
+  p.q = reinterpret_cast<const bf16_t*>(q); p.ldq = ldq;
+  p.k = reinterpret_cast<const bf16_t*>(k); p.ldk = ldk;
+  p.v = reinterpret_cast<const bf16_t*>(v); p.ldv = ldv;
+  p.o = reinterpret_cast<const bf16_t*>(o); p.ldo = ldo;
+  p.dout = reinterpret_cast<const bf16_t*>(dout); p.lddo = lddo;
+  p.dq = reinterpret_cast<bf16_t*>(dq); p.lddq = lddq;
+  p.B = B; p.N = N; p.heads = heads; p.d = d;
+  return p;
+}
+
+int hedit_k_attn_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o, int ldo,
+                     const void* dout, int lddo, void* dq, int lddq, void* dk, void* dv, int B, int N, int heads, int d,
+                     void* ws, void* stream) try {
+  ARG_CHECK(q && k && v && o && dout && dq && dk && dv && ws, "attn_bwd args");
+  AttnBwdParams p = attn_bwd_params(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, dq, lddq, B, N, heads, d);
+  p.dk = reinterpret_cast<bf16_t*>(dk); p.dv = reinterpret_cast<bf16_t*>(dv); p.lddkv = heads * d;
+  p.stats = reinterpret_cast<float*>(ws);
+  p.M = N; p.kstride = N;
+  return attn_bwd_launch(p, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_cross_attn_bwd_q(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o, int ldo,
+                             const void* dout, int lddo, void* dq, int lddq, int B, int N, int heads, int d, void* stream) try {
+  ARG_CHECK(q && k && v && o && dout && dq, "cross_attn_bwd_q args");
+  AttnBwdParams p = attn_bwd_params(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, dq, lddq, B, N, heads, d);
+  p.M = HEDIT_MAXW; p.kstride = HEDIT_CTXP;
+  return attn_bwd_launch(p, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_groupnorm_bwd_any(const void* x, const void* dy, const void* add, void* dx, const float* gamma, const float* beta,
+                              const float* stats, int B, int HW, int C, int G, int silu, void* ws, void* stream) try {
+  ARG_CHECK(x && dy && dx && gamma && beta && stats && ws, "groupnorm_bwd_any args");
+  return groupnorm_bwd_launch(reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(dy),
+                              reinterpret_cast<const bf16_t*>(add), reinterpret_cast<bf16_t*>(dx), gamma, beta, stats, B, HW, C,
+                              G, silu, reinterpret_cast<float*>(ws), S(stream), true);
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_layernorm_bwd(const void* x, const void* dy, const void* add, void* dx, const float* gamma, int64_t rows, int C,
+                          float eps, void* stream) try {
+  ARG_CHECK(x && dy && dx && gamma, "layernorm_bwd args");
+  return layernorm_bwd_launch(reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(dy),
+                              reinterpret_cast<const bf16_t*>(add), reinterpret_cast<bf16_t*>(dx), gamma, (long)rows, C, eps, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_geglu_bwd(const void* x, const void* dy, void* dx, int64_t rows, int inner, void* stream) try {
+  ARG_CHECK(x && dy && dx, "geglu_bwd args");
+  return geglu_bwd_launch(reinterpret_cast<const bf16_t*>(x), reinterpret_cast<const bf16_t*>(dy), reinterpret_cast<bf16_t*>(dx),
+                          (long)rows, inner, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_conv3x3_s2_dgrad_pad1(const void* dy, const void* w_packed, void* dx, int B, int Hin, int Win, int O, int I,
+                                  void* stream) try {
+  ARG_CHECK(dy && w_packed && dx, "conv3x3_s2_dgrad_pad1 args");
+  return conv3x3_s2_dgrad_pad1_launch(reinterpret_cast<const bf16_t*>(dy), reinterpret_cast<const bf16_t*>(w_packed),
+                                      reinterpret_cast<bf16_t*>(dx), B, Hin, Win, O, I, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
 int hedit_k_pack_linear_t(const float* w, void* out, int O, int I, void* stream) try {
   ARG_CHECK(w && out, "pack args");
   return pack_linear_t_launch(w, reinterpret_cast<bf16_t*>(out), O, I, S(stream));

@@ -20,7 +20,9 @@ __device__ __forceinline__ float silu_grad(float z) {
 // forward: xh = (x - mu_g) r_g ; z = gamma xh + beta ; y = silu(z) | z
 // backward: t = dz gamma ; dx = r_g (t - mean_g(t) - xh mean_g(t xh))
 // stage 1: per (batch, pixel slab) partial sums of t and t*xh per group
-__global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
+// NT threads: 256, or 512 for rows wider than 2048 channels (the SD UNet's widest skip concatenations, C = 2560)
+template <int NT>
+__global__ __launch_bounds__(NT) void gn_bwd_partial_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
                                                              const float* __restrict__ stats, float* __restrict__ part,
                                                              int HW, int C, int G, int nslab, int silu) {
@@ -31,7 +33,7 @@ __global__ __launch_bounds__(256) void gn_bwd_partial_kernel(const bf16_t* __res
   const int p0 = slab * pix_per;
   int p1 = p0 + pix_per;
   if (p1 > HW) p1 = HW;
-  const int R = 256 / CV;
+  const int R = NT / CV;
   const int r = threadIdx.x / CV, cv = threadIdx.x % CV;
   const int cpg = C / G;
   float s[8], q[8];
@@ -122,7 +124,8 @@ __global__ __launch_bounds__(256) void gn_bwd_finalize_kernel(const float* __res
 
 // stage 3: dx = A dz - B x + E (+ add), dz = dy * silu'(A x + D).  Same thread layout as stage 1: a thread
 // keeps the coefficients of its 8 channels in registers over the pixels of its slab.
-__global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
+template <int NT>
+__global__ __launch_bounds__(NT) void gn_bwd_apply_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
                                                            const bf16_t* __restrict__ add, bf16_t* __restrict__ dx,
                                                            const float* __restrict__ coef, int HW, int C, int nslab, int silu) {
   const int CV = C / 8;
@@ -131,7 +134,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const bf16_t* __restr
   const int p0 = slab * pix_per;
   int p1 = p0 + pix_per;
   if (p1 > HW) p1 = HW;
-  const int R = 256 / CV;
+  const int R = NT / CV;
   const int r = threadIdx.x / CV, cv = threadIdx.x % CV;
   if (r >= R) return;
   float4 k[8];
@@ -159,7 +162,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(const bf16_t* __restr
 // slabs per image: a function of (HW, C) only, like gn_nslab -- the gradient of an image does not depend on the batch
 int gb_nslab(int B, int HW, int C) {
   (void)B;
-  const int R = 256 / (C / 8);
+  const int R = (C / 8 > 256 ? 512 : 256) / (C / 8);
   int n = HW / (R * 8);
   int cap = HW / 1024;
   cap = cap < 32 ? 32 : (cap > 128 ? 128 : cap);
@@ -193,6 +196,103 @@ __global__ __launch_bounds__(256) void softmax_bwd_kernel(const bf16_t* __restri
     o.x = pack_bf16x2(scale * bf16_to_f32((bf16_t)(u.x & 0xffff)) * (d[0] - dot), scale * bf16_to_f32((bf16_t)(u.x >> 16)) * (d[1] - dot));
     o.y = pack_bf16x2(scale * bf16_to_f32((bf16_t)(u.y & 0xffff)) * (d[2] - dot), scale * bf16_to_f32((bf16_t)(u.y >> 16)) * (d[3] - dot));
     *reinterpret_cast<uint2*>(out + i) = o;
+  }
+}
+
+// ------------------------------------------------------------------ LayerNorm backward, one wave per row
+// forward: xh = (x - mu) r ; y = gamma xh + beta.  backward: t = dy gamma ; dx = r (t - mean(t) - xh mean(t xh)) (+ add).
+// mu and r are recomputed from the kept x in fp32, in layernorm_kernel's order.
+constexpr int LNB_MAXV = 3;   // C up to 1536
+__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
+                                                            const bf16_t* __restrict__ add, bf16_t* __restrict__ dx,
+                                                            const float* __restrict__ gamma, long rows, int C, float eps) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int CV = C / 8;
+  float f[LNB_MAXV][8], t[LNB_MAXV][8];
+  float s = 0.f;
+#pragma unroll
+  for (int v = 0; v < LNB_MAXV; ++v) {
+    const int cv = lane + v * 64;
+    if (cv < CV) {
+      unpack8(*reinterpret_cast<const uint4*>(x + row * C + cv * 8), f[v]);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) s += f[v][j];
+    }
+  }
+  const float mean = wave_sum(s) / (float)C;
+  float q = 0.f;
+#pragma unroll
+  for (int v = 0; v < LNB_MAXV; ++v) {
+    const int cv = lane + v * 64;
+    if (cv < CV) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) { const float d = f[v][j] - mean; q += d * d; }
+    }
+  }
+  const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int v = 0; v < LNB_MAXV; ++v) {
+    const int cv = lane + v * 64;
+    if (cv < CV) {
+      float d[8];
+      unpack8(*reinterpret_cast<const uint4*>(dy + row * C + cv * 8), d);
+      const float4* g4 = reinterpret_cast<const float4*>(gamma + cv * 8);
+      const float4 g0 = g4[0], g1 = g4[1];
+      const float g[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        f[v][j] = (f[v][j] - mean) * rstd;   // xh from here on
+        t[v][j] = d[j] * g[j];
+        s1 += t[v][j];
+        s2 += t[v][j] * f[v][j];
+      }
+    }
+  }
+  const float m1 = wave_sum(s1) / (float)C, m2 = wave_sum(s2) / (float)C;
+#pragma unroll
+  for (int v = 0; v < LNB_MAXV; ++v) {
+    const int cv = lane + v * 64;
+    if (cv < CV) {
+      float o[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = rstd * (t[v][j] - m1 - f[v][j] * m2);
+      if (add) {
+        float a[8];
+        unpack8(*reinterpret_cast<const uint4*>(add + row * C + cv * 8), a);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) o[j] += a[j];
+      }
+      *reinterpret_cast<uint4*>(dx + row * C + cv * 8) = pack8(o);
+    }
+  }
+}
+
+// ------------------------------------------------------------------ GEGLU backward: y = h gelu(g), x = [h | g] -> dx = [dh | dg]
+// dh = dy gelu(g), dg = dy h gelu'(g) with the exact GELU: gelu'(g) = Phi(g) + g phi(g)
+__global__ __launch_bounds__(256) void geglu_bwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dy,
+                                                        bf16_t* __restrict__ dx, long rows, int inner) {
+  const int IV = inner / 8;
+  const long total = rows * IV;
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
+    const long row = i / IV;
+    const int v = (int)(i - row * IV);
+    const long o = row * (2L * inner) + v * 8;
+    float h[8], g[8], d[8], dh[8], dg[8];
+    unpack8(*reinterpret_cast<const uint4*>(x + o), h);
+    unpack8(*reinterpret_cast<const uint4*>(x + o + inner), g);
+    unpack8(*reinterpret_cast<const uint4*>(dy + row * inner + v * 8), d);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const float cdf = 0.5f * (1.0f + erff(g[j] * 0.70710678118654752f));
+      const float pdf = 0.3989422804014327f * __expf(-0.5f * g[j] * g[j]);
+      dh[j] = d[j] * g[j] * cdf;
+      dg[j] = d[j] * h[j] * (cdf + g[j] * pdf);
+    }
+    *reinterpret_cast<uint4*>(dx + o) = pack8(dh);
+    *reinterpret_cast<uint4*>(dx + o + inner) = pack8(dg);
   }
 }
 
@@ -257,12 +357,12 @@ __global__ __launch_bounds__(256) void pack_conv3x3_dgrad_kernel(const float* __
   }
 }
 // [O][I] fp32 -> bf16 [I][O]
-__global__ __launch_bounds__(256) void pack_linear_t_kernel(const float* __restrict__ w, bf16_t* __restrict__ out, int O, int I) {
+__global__ __launch_bounds__(256) void pack_linear_t_kernel(const float* __restrict__ w, bf16_t* __restrict__ out, int O, int I, float scale) {
   const long total = (long)O * I;
   for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
     const int o = (int)(idx % O);
     const int i = (int)(idx / O);
-    out[idx] = f32_to_bf16(w[(long)o * I + i]);
+    out[idx] = f32_to_bf16(w[(long)o * I + i] * scale);
   }
 }
 // OIHW fp32 (k x k) -> IOHW fp32 with the taps flipped (k = 1: a plain transpose)
@@ -288,15 +388,21 @@ int groupnorm_bwd_launch(const bf16_t* x, const bf16_t* dy, const bf16_t* add, b
                          hipStream_t st, bool any_width) {
   // any_width: C / 8 need not divide the block -- the kernels then run R = 256 / (C / 8) pixel rows per pass and leave the
   // last 256 - R * C / 8 threads idle (every stage guards r < R): the skip concatenations of the pixel UNet (C = 192, 384, 768)
-  ARG_CHECK(C % 8 == 0 && C % G == 0 && G <= 64 && C / 8 <= 256 && (any_width || 256 % (C / 8) == 0),
+  ARG_CHECK(C % 8 == 0 && C % G == 0 && G <= 64 && C / 8 <= (any_width ? 512 : 256) && (any_width || 256 % (C / 8) == 0),
             "groupnorm_bwd: C % 8, C % G, G <= 64, C/8 a divisor of 256");
   const int nslab = gb_nslab(B, HW, C);
   float* part = ws;
   float* coef = ws + (size_t)B * nslab * 64 * 2;
-  const int R = 256 / (C / 8);
+  const bool wide = C / 8 > 256;
+  const int R = (wide ? 512 : 256) / (C / 8);
   const size_t lds = (size_t)R * C * 2 * sizeof(float);
-  hipLaunchKernelGGL(gn_bwd_partial_kernel, dim3(nslab, B), dim3(256), lds, st, x, dy, gamma, beta, stats, part, HW, C, G,
-                     nslab, silu);
+  if (wide) {
+    hipLaunchKernelGGL(gn_bwd_partial_kernel<512>, dim3(nslab, B), dim3(512), lds, st, x, dy, gamma, beta, stats, part, HW, C, G,
+                       nslab, silu);
+  } else {
+    hipLaunchKernelGGL(gn_bwd_partial_kernel<256>, dim3(nslab, B), dim3(256), lds, st, x, dy, gamma, beta, stats, part, HW, C, G,
+                       nslab, silu);
+  }
   LAUNCH_CHECK();
   hipLaunchKernelGGL(gn_bwd_finalize_kernel, dim3(B), dim3(256), 0, st, part, gamma, beta, stats, coef, HW, C, G, nslab);
   LAUNCH_CHECK();
@@ -304,7 +410,11 @@ int groupnorm_bwd_launch(const bf16_t* x, const bf16_t* dy, const bf16_t* add, b
   int na = HW / (R * 16);
   if (na > 2048) na = 2048;
   if (na < 1) na = 1;
-  hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(na, B), dim3(256), 0, st, x, dy, add, dx, coef, HW, C, na, silu);
+  if (wide) {
+    hipLaunchKernelGGL(gn_bwd_apply_kernel<512>, dim3(na, B), dim3(512), 0, st, x, dy, add, dx, coef, HW, C, na, silu);
+  } else {
+    hipLaunchKernelGGL(gn_bwd_apply_kernel<256>, dim3(na, B), dim3(256), 0, st, x, dy, add, dx, coef, HW, C, na, silu);
+  }
   LAUNCH_CHECK();
   return HEDIT_OK;
 }
@@ -337,14 +447,29 @@ int pack_conv3x3_dgrad_launch(const float* w_oihw, bf16_t* out, int O, int I, hi
   return HEDIT_OK;
 }
 
-int pack_linear_t_launch(const float* w, bf16_t* out, int O, int I, hipStream_t st) {
-  hipLaunchKernelGGL(pack_linear_t_kernel, dim3(ew_grid((long)O * I)), dim3(256), 0, st, w, out, O, I);
+int pack_linear_t_launch(const float* w, bf16_t* out, int O, int I, hipStream_t st, float scale) {
+  hipLaunchKernelGGL(pack_linear_t_kernel, dim3(ew_grid((long)O * I)), dim3(256), 0, st, w, out, O, I, scale);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }
 
 int flip_oihw_launch(const float* w, float* out, int O, int I, int k, hipStream_t st) {
   hipLaunchKernelGGL(flip_oihw_kernel, dim3(ew_grid((long)O * I * k * k)), dim3(256), 0, st, w, out, O, I, k * k);
+  LAUNCH_CHECK();
+  return HEDIT_OK;
+}
+
+int layernorm_bwd_launch(const bf16_t* x, const bf16_t* dy, const bf16_t* add, bf16_t* dx, const float* gamma, long rows, int C,
+                         float eps, hipStream_t st) {
+  ARG_CHECK(rows >= 1 && C >= 8 && C % 8 == 0 && C <= LNB_MAXV * 512, "layernorm_bwd: C a multiple of 8, at most 1536");
+  hipLaunchKernelGGL(layernorm_bwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, st, x, dy, add, dx, gamma, rows, C, eps);
+  LAUNCH_CHECK();
+  return HEDIT_OK;
+}
+
+int geglu_bwd_launch(const bf16_t* x, const bf16_t* dy, bf16_t* dx, long rows, int inner, hipStream_t st) {
+  ARG_CHECK(rows >= 1 && inner >= 8 && inner % 8 == 0, "geglu_bwd: inner a multiple of 8");
+  hipLaunchKernelGGL(geglu_bwd_kernel, dim3(ew_grid(rows * (inner / 8))), dim3(256), 0, st, x, dy, dx, rows, inner);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }

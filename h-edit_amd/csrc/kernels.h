@@ -191,14 +191,21 @@ int sum2x2_launch(const bf16_t* du, bf16_t* dx, int B, int H, int W, int C, hipS
 // weights of the input-gradient GEMMs: conv3x3 OIHW -> bf16 [I][9][O] taps flipped; linear [O][I] -> bf16 [I][O];
 // k x k OIHW fp32 -> IOHW fp32 taps flipped
 int pack_conv3x3_dgrad_launch(const float* w_oihw, bf16_t* out, int O, int I, hipStream_t st);
-int pack_linear_t_launch(const float* w, bf16_t* out, int O, int I, hipStream_t st);
+int pack_linear_t_launch(const float* w, bf16_t* out, int O, int I, hipStream_t st, float scale = 1.f);   // out = (scale * w)^T
 int flip_oihw_launch(const float* w, float* out, int O, int I, int k, hipStream_t st);
+// LayerNorm backward over rows of width C (C % 8 == 0, C <= 1536): mean / rstd recomputed from the kept x; dx (+ add, if given)
+int layernorm_bwd_launch(const bf16_t* x, const bf16_t* dy, const bf16_t* add, bf16_t* dx, const float* gamma, long rows, int C,
+                         float eps, hipStream_t st);
+// GEGLU backward: x = the FF1 pre-activation [rows][2 inner] = [value | gate], dy [rows][inner] -> dx [rows][2 inner]
+int geglu_bwd_launch(const bf16_t* x, const bf16_t* dy, bf16_t* dx, long rows, int inner, hipStream_t st);
 
 // ---------------------------------------------------------------- s2dgrad.hip (pixel UNet input-gradient pieces)
 // dx [B][Hin][Win][I] = input gradient of the stride-2 3x3 conv with pad (0,1,0,1) applied to dy [B][Hin/2][Win/2][O];
 // wt = bf16 [I][9][O] from pack_conv3x3_s2_dgrad_launch (taps in place).  O % 64 == 0, I % 64 == 0, Hin and Win even.
 int conv3x3_s2_dgrad_launch(const bf16_t* dy, const bf16_t* wt, bf16_t* dx, int B, int Hin, int Win, int O, int I, hipStream_t st);
 int pack_conv3x3_s2_dgrad_launch(const float* w_oihw, bf16_t* out, int O, int I, hipStream_t st);
+// the same for padding 1 all round (the SD UNet's Downsample2D): same packed weight, the parities mirrored (1 / 2 / 2 / 4 taps)
+int conv3x3_s2_dgrad_pad1_launch(const bf16_t* dy, const bf16_t* wt, bf16_t* dx, int B, int Hin, int Win, int O, int I, hipStream_t st);
 // dst [rows][c] = src [rows][ld] columns [off, off + c) (accumulate = 0), or dst = round(fp32(dst) + fp32(src columns));
 // c, off, ld multiples of 8.  Backward of the skip concatenation.
 int slice_add_launch(const bf16_t* src, int ld, int off, int c, bf16_t* dst, long rows, int accumulate, hipStream_t st);
@@ -250,6 +257,22 @@ struct AttnProbsParams {
 int attn_probs_launch(const AttnProbsParams& p, hipStream_t st);
 int attn_self_store_launch(const AttnProbsParams& p, hipStream_t st);
 int attn_apply_launch(const AttnProbsParams& p, hipStream_t st);
+
+// ---------------------------------------------------------------- attnbwd.hip
+// Attention backward, flash style (no T x T tensor, no atomics).  Plain attention only (no qk_src / kv_src, no P2P mixing).
+struct AttnBwdParams {
+  const bf16_t* q; int ldq;       // [B*N][ldq], head h at column h*d; pre-scaled by scale*log2(e)
+  const bf16_t* k; int ldk;       // [B*kstride][ldk]
+  const bf16_t* v; int ldv;       // [B*kstride][ldv], row-major like k
+  const bf16_t* o; int ldo;       // [B*N][ldo]: the forward's output
+  const bf16_t* dout; int lddo;   // [B*N][lddo]: its gradient
+  bf16_t* dq; int lddq;           // [B*N][lddq]: gradient w.r.t. the pre-scaled q
+  bf16_t* dk; bf16_t* dv; int lddkv;   // [B*N][lddkv] each, or both null (then M keys of kstride rows per image: the context form)
+  float* stats;                   // attn_bwd_ws_bytes: (lse, delta) per (image, head, query); needed with dk / dv
+  int B, N, M, kstride, heads, d;
+};
+size_t attn_bwd_ws_bytes(int B, int N, int heads);
+int attn_bwd_launch(const AttnBwdParams& p, hipStream_t st);
 
 // ---------------------------------------------------------------- step.hip
 struct StepCoef {

@@ -24,7 +24,10 @@ namespace {
 
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;   // (not HIP's uint4 struct: its aggregate copies defeat SROA)
 
-template <int BN>
+// PAD1: the symmetric padding 1 of the SD UNet's Downsample2D instead: y[o,p] = sum W[a,b] x[2o+a-1, 2p+b-1], so a dx pixel
+// takes the taps with i + 1 - a even -- the parities mirrored: even rows a = 1 (dy row u for i = 2u), odd rows a in {0, 2}
+// (dy rows u + 1, u for i = 2u + 1; row Hq is outside) -> 1 / 2 / 2 / 4 taps.
+template <int BN, bool PAD1 = false>
 __global__ __launch_bounds__(256) void conv3x3_s2_dgrad_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ wt,
                                                                bf16_t* __restrict__ dx, int B, int Hq, int Wq, int O, int I) {
   constexpr int BM = 64, BK = 64;
@@ -38,7 +41,7 @@ __global__ __launch_bounds__(256) void conv3x3_s2_dgrad_kernel(const bf16_t* __r
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
   const int ph = blockIdx.z, pi = ph >> 1, pj = ph & 1;
-  const int ny = pi ? 1 : 2, nx = pj ? 1 : 2, ntap = ny * nx;
+  const int ny = (pi != 0) == PAD1 ? 2 : 1, nx = (pj != 0) == PAD1 ? 2 : 1, ntap = ny * nx;
   const long Mq = (long)B * Hq * Wq;
   const long m0 = (long)blockIdx.x * BM;
   const int n0 = blockIdx.y * BN;
@@ -62,13 +65,19 @@ __global__ __launch_bounds__(256) void conv3x3_s2_dgrad_kernel(const bf16_t* __r
   auto load_tile = [&](int kt) __attribute__((always_inline)) {
     const int tap = kt % ntap, slab = kt / ntap;
     const int ty = tap / nx, tx = tap - ty * nx;
-    const int sy = pi ? 0 : ty, sx = pj ? 0 : tx;             // dy row / column shift (u - sy, v - sx)
-    const int a9 = (pi ? 1 : 2 * ty) * 3 + (pj ? 1 : 2 * tx);  // the tap's index in the 3x3 filter
+    int sy, sx, a9;
+    if constexpr (PAD1) {
+      sy = pi ? ty - 1 : 0, sx = pj ? tx - 1 : 0;               // dy rows u + 1 (a = 0), u (a = 2)
+      a9 = (pi ? 2 * ty : 1) * 3 + (pj ? 2 * tx : 1);
+    } else {
+      sy = pi ? 0 : ty, sx = pj ? 0 : tx;                       // dy row / column shift (u - sy, v - sx)
+      a9 = (pi ? 1 : 2 * ty) * 3 + (pj ? 1 : 2 * tx);           // the tap's index in the 3x3 filter
+    }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       const int u = a_u[i] - sy, v = a_v[i] - sx;
       ra[i] = (u32x4){0u, 0u, 0u, 0u};
-      if (a_ok[i] && u >= 0 && v >= 0)
+      if (a_ok[i] && u >= 0 && v >= 0 && (!PAD1 || (u < Hq && v < Wq)))
         ra[i] = *reinterpret_cast<const u32x4*>(dy + (((long)a_b[i] * Hq + u) * Wq + v) * O + slab * BK + c8);
     }
 #pragma unroll
@@ -177,7 +186,9 @@ __global__ __launch_bounds__(256) void slice_add_kernel(const bf16_t* __restrict
 
 }  // namespace
 
-int conv3x3_s2_dgrad_launch(const bf16_t* dy, const bf16_t* wt, bf16_t* dx, int B, int Hin, int Win, int O, int I, hipStream_t st) {
+namespace {
+template <bool PAD1>
+int s2_dgrad_launch(const bf16_t* dy, const bf16_t* wt, bf16_t* dx, int B, int Hin, int Win, int O, int I, hipStream_t st) {
   ARG_CHECK(B >= 1 && Hin >= 2 && Win >= 2 && Hin % 2 == 0 && Win % 2 == 0, "conv3x3_s2_dgrad: even input height and width");
   ARG_CHECK(O % 64 == 0 && I % 64 == 0, "conv3x3_s2_dgrad: channel counts must be multiples of 64");
   const int Hq = Hin / 2, Wq = Win / 2;
@@ -185,14 +196,22 @@ int conv3x3_s2_dgrad_launch(const bf16_t* dy, const bf16_t* wt, bf16_t* dx, int 
   ARG_CHECK(Mq * 4 * (I > O ? I : O) < (1L << 40) && (Mq + 63) / 64 < (1L << 31), "conv3x3_s2_dgrad: tensor too large");
   // the 128-channel tile re-uses an activation fragment twice as often; the narrow one keeps small layers spread over the CUs
   if (I % 128 == 0 && Mq >= 4096) {
-    hipLaunchKernelGGL(conv3x3_s2_dgrad_kernel<128>, dim3((unsigned)((Mq + 63) / 64), I / 128, 4), dim3(256), 0, st, dy, wt, dx, B, Hq,
+    hipLaunchKernelGGL((conv3x3_s2_dgrad_kernel<128, PAD1>), dim3((unsigned)((Mq + 63) / 64), I / 128, 4), dim3(256), 0, st, dy, wt, dx, B, Hq,
                        Wq, O, I);
   } else {
-    hipLaunchKernelGGL(conv3x3_s2_dgrad_kernel<64>, dim3((unsigned)((Mq + 63) / 64), I / 64, 4), dim3(256), 0, st, dy, wt, dx, B, Hq,
+    hipLaunchKernelGGL((conv3x3_s2_dgrad_kernel<64, PAD1>), dim3((unsigned)((Mq + 63) / 64), I / 64, 4), dim3(256), 0, st, dy, wt, dx, B, Hq,
                        Wq, O, I);
   }
   LAUNCH_CHECK();
   return HEDIT_OK;
+}
+}  // namespace
+
+int conv3x3_s2_dgrad_launch(const bf16_t* dy, const bf16_t* wt, bf16_t* dx, int B, int Hin, int Win, int O, int I, hipStream_t st) {
+  return s2_dgrad_launch<false>(dy, wt, dx, B, Hin, Win, O, I, st);
+}
+int conv3x3_s2_dgrad_pad1_launch(const bf16_t* dy, const bf16_t* wt, bf16_t* dx, int B, int Hin, int Win, int O, int I, hipStream_t st) {
+  return s2_dgrad_launch<true>(dy, wt, dx, B, Hin, Win, O, I, st);
 }
 
 int pack_conv3x3_s2_dgrad_launch(const float* w_oihw, bf16_t* out, int O, int I, hipStream_t st) {

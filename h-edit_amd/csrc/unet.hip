@@ -37,12 +37,19 @@ struct Slot {
   int ndim;
   int dims[4];
   int which = 0, lay = 0;
+  // hedit_unet_create_grad: further destinations the same checkpoint tensor is packed into (the input-gradient twins, and at
+  // the chain width the unfused forward weights).  kind: 0 fp32 copy, 1 linear -> bf16 (scaled), 10 linear [O][I] -> bf16 [I][O]
+  // (scaled), 11 conv3x3 -> bf16 [I][9][O] taps flipped, 12 the same with the taps in place (stride-2 dgrad), 13 OIHW -> fp32
+  // IOHW taps flipped
+  struct Extra { int kind; void* dst; float scale; int O, I; };
+  std::vector<Extra> extra;
 };
 
 struct Res {
   int cin, cout, temb_off;
   float *n1g, *n1b, *n2g, *n2b, *conv2_b, *sc_b;
   bf16_t *conv1, *conv2, *sc_w;
+  bf16_t *conv1_t = nullptr, *conv2_t = nullptr, *sc_t = nullptr;   // input-gradient weights (hedit_unet_create_grad)
 };
 
 struct Attn {
@@ -54,6 +61,12 @@ struct Attn {
   bf16_t *frs = nullptr, *k1s = nullptr, *ffs = nullptr;
   float* ff1_bp = nullptr;
   int ctx_off = 0;      // first row of this block's attn2.to_k / to_v in the UNet-wide matrices (hedit_unet::wk2_all / wv2_all)
+  // hedit_unet_create_grad: transposed weights ([I][O]; the two queries with their scale), FF1 in the checkpoint's row order
+  // (value rows, then gate rows) with its bias -- the taped forward keeps the FF1 pre-activation --, and at the chain width
+  // the unfused forward weights above as well
+  bf16_t *pin_t = nullptr, *wq1_t = nullptr, *wk1_t = nullptr, *wv1_t = nullptr, *wo1_t = nullptr, *wq2_t = nullptr, *wo2_t = nullptr,
+         *ff1_t = nullptr, *ff2_t = nullptr, *pout_t = nullptr, *ff1n = nullptr;
+  float* ff1_bn = nullptr;
 };
 
 struct Block {
@@ -61,6 +74,7 @@ struct Block {
   std::vector<Attn> attn;
   bool has_attn = false, has_sampler = false;
   bf16_t* samp_w = nullptr;
+  bf16_t* samp_t = nullptr;     // input-gradient weight of the sampler: down [I][9][O] taps in place, up taps flipped
   float* samp_b = nullptr;
   int ch = 0;
 };
@@ -100,6 +114,13 @@ struct hedit_unet {
   // hedit_unet_workspace_bytes by (B, height, width, hook set): the answer covers every row map, i.e. one dry run per
   // number of distinct latents, so it is worked out once per shape
   std::map<std::array<int, 4>, size_t> ws_cache;
+  // hedit_unet_create_grad only: input-gradient twins of the head / tail convolutions, a zero bias vector, and the
+  // outstanding tape of hedit_unet_forward_keep (a GradTape, unetgrad.h)
+  bool grad = false;
+  bf16_t* conv_in_t = nullptr;
+  float *conv_out_t = nullptr, *zero_bias = nullptr;
+  void* tape = nullptr;
+  void (*tape_free)(void*) = nullptr;
 };
 
 namespace {
@@ -140,21 +161,39 @@ bf16_t* conv3p(hedit_unet* h, const std::string& name, int O, int I) {
   return dst;
 }
 
+// grad handle: one more destination for the slot just added
+template <class T>
+T* add_extra(hedit_unet* h, int kind, T* dst, size_t n, int O, int I, float scale = 1.f) {
+  if (!dst) dst = dalloc<T>(h, n);
+  h->slots.back().extra.push_back({kind, dst, scale, O, I});
+  return dst;
+}
+// grad handle: the linear slot just added also fills its transposed twin *t and, where the forward-only handle keeps the
+// weight in a chain stream only (fwd != nullptr), the unfused forward copy *fwd (allocated here unless it is set)
+void grad_lin(hedit_unet* h, int O, int I, float scale, bf16_t** t, bf16_t** fwd = nullptr) {
+  if (!h->grad) return;
+  *t = add_extra<bf16_t>(h, 10, nullptr, (size_t)O * I, O, I, scale);
+  if (fwd) *fwd = add_extra<bf16_t>(h, 1, *fwd, (size_t)O * I, O, I, scale);
+}
+
 Res make_res(hedit_unet* h, const std::string& pre, int cin, int cout, int& temb_off) {
   Res r{};
   r.cin = cin; r.cout = cout; r.temb_off = temb_off;
   r.n1g = f32p(h, pre + ".norm1.weight", cin);
   r.n1b = f32p(h, pre + ".norm1.bias", cin);
   r.conv1 = conv3p(h, pre + ".conv1.weight", cout, cin);
+  if (h->grad) r.conv1_t = add_extra<bf16_t>(h, 11, nullptr, (size_t)cout * cin * 9, cout, cin);
   f32p(h, pre + ".conv1.bias", cout, h->conv1_b_all + temb_off);
   linp(h, pre + ".time_emb_proj.weight", cout, h->temb_dim, h->temb_w_all + (size_t)temb_off * h->temb_dim);
   f32p(h, pre + ".time_emb_proj.bias", cout, h->temb_b_all + temb_off);
   r.n2g = f32p(h, pre + ".norm2.weight", cout);
   r.n2b = f32p(h, pre + ".norm2.bias", cout);
   r.conv2 = conv3p(h, pre + ".conv2.weight", cout, cout);
+  if (h->grad) r.conv2_t = add_extra<bf16_t>(h, 11, nullptr, (size_t)cout * cout * 9, cout, cout);
   r.conv2_b = f32p(h, pre + ".conv2.bias", cout);
   if (cin != cout) {
     r.sc_w = linp(h, pre + ".conv_shortcut.weight", cout, cin);
+    grad_lin(h, cout, cin, 1.f, &r.sc_t);
     r.sc_b = f32p(h, pre + ".conv_shortcut.bias", cout);
   }
   temb_off += cout;
@@ -190,26 +229,42 @@ Attn make_attn(hedit_unet* h, const std::string& pre, int C) {
   } else {
     a.pin = linp(h, pre + ".proj_in.weight", C, C);
   }
+  grad_lin(h, C, C, 1.f, &a.pin_t, chain ? &a.pin : nullptr);
   a.pin_b = f32p(h, pre + ".proj_in.bias", C);
   a.ln1g = f32p(h, tb + ".norm1.weight", C);
   a.ln1b = f32p(h, tb + ".norm1.bias", C);
   if (chain) {
+    bf16_t *wq = nullptr, *wk = nullptr;
+    if (h->grad) {
+      a.w_qk = dalloc<bf16_t>(h, (size_t)2 * C * C);
+      wq = a.w_qk;
+      wk = a.w_qk ? a.w_qk + (size_t)C * C : nullptr;
+    }
     stream_slot(tb + ".attn1.to_q.weight", a.frs, 4, 1, C, C, qscale, 2);
+    grad_lin(h, C, C, qscale, &a.wq1_t, &wq);
     stream_slot(tb + ".attn1.to_k.weight", a.frs, 4, 2, C, C, 1.f, 2);
+    grad_lin(h, C, C, 1.f, &a.wk1_t, &wk);
     stream_slot(tb + ".attn1.to_v.weight", a.frs, 4, 3, C, C, 1.f, 2);
+    grad_lin(h, C, C, 1.f, &a.wv1_t, &a.w_v1);
     stream_slot(tb + ".attn1.to_out.0.weight", a.k1s, 2, 0, C, C, 1.f, 2);
+    grad_lin(h, C, C, 1.f, &a.wo1_t, &a.w_o1);
   } else {
     a.w_qk = dalloc<bf16_t>(h, (size_t)2 * C * C);
     linp(h, tb + ".attn1.to_q.weight", C, C, a.w_qk, qscale);
+    grad_lin(h, C, C, qscale, &a.wq1_t);
     linp(h, tb + ".attn1.to_k.weight", C, C, a.w_qk + (size_t)C * C);
+    grad_lin(h, C, C, 1.f, &a.wk1_t);
     a.w_v1 = linp(h, tb + ".attn1.to_v.weight", C, C);
+    grad_lin(h, C, C, 1.f, &a.wv1_t);
     a.w_o1 = linp(h, tb + ".attn1.to_out.0.weight", C, C);
+    grad_lin(h, C, C, 1.f, &a.wo1_t);
   }
   a.o1_b = f32p(h, tb + ".attn1.to_out.0.bias", C);
   a.ln2g = f32p(h, tb + ".norm2.weight", C);
   a.ln2b = f32p(h, tb + ".norm2.bias", C);
   if (chain) stream_slot(tb + ".attn2.to_q.weight", a.k1s, 2, 1, C, C, qscale, 2);
   else a.w_q2 = linp(h, tb + ".attn2.to_q.weight", C, C, nullptr, qscale);
+  grad_lin(h, C, C, qscale, &a.wq2_t, chain ? &a.w_q2 : nullptr);
   a.ctx_off = h->ctx_next;
   h->ctx_next += C;
   a.w_k2 = linp(h, tb + ".attn2.to_k.weight", C, ctx, h->wk2_all + (size_t)a.ctx_off * ctx);
@@ -219,19 +274,26 @@ Attn make_attn(hedit_unet* h, const std::string& pre, int C) {
   } else {
     a.w_o2 = linp(h, tb + ".attn2.to_out.0.weight", C, C);
   }
+  grad_lin(h, C, C, 1.f, &a.wo2_t, chain ? &a.w_o2 : nullptr);
   a.o2_b = f32p(h, tb + ".attn2.to_out.0.bias", C);
   a.ln3g = f32p(h, tb + ".norm3.weight", C);
   a.ln3b = f32p(h, tb + ".norm3.bias", C);
   if (chain) {
     stream_slot(tb + ".ff.net.0.proj.weight", a.ffs, 0, 1, 8 * C, C, 1.f, 2);
+    grad_lin(h, 8 * C, C, 1.f, &a.ff1_t, &a.ff1n);
     add_slot(h, tb + ".ff.net.0.proj.bias", 6, a.ff1_bp, (size_t)8 * C);
+    if (h->grad) a.ff1_bn = add_extra<float>(h, 0, nullptr, (size_t)8 * C, 0, 0);
     stream_slot(tb + ".ff.net.2.weight", a.ffs, 0, 2, C, 4 * C, 1.f, 2);
+    grad_lin(h, C, 4 * C, 1.f, &a.ff2_t, &a.ff2);
   } else {
     a.ff1 = linp(h, tb + ".ff.net.0.proj.weight", 8 * C, C);
     h->slots.back().kind = 3;
+    grad_lin(h, 8 * C, C, 1.f, &a.ff1_t, &a.ff1n);
     a.ff1_b = f32p(h, tb + ".ff.net.0.proj.bias", 8 * C);
     h->slots.back().kind = 4;
+    if (h->grad) a.ff1_bn = add_extra<float>(h, 0, nullptr, (size_t)8 * C, 0, 0);
     a.ff2 = linp(h, tb + ".ff.net.2.weight", C, 4 * C);
+    grad_lin(h, C, 4 * C, 1.f, &a.ff2_t);
   }
   a.ff2_b = f32p(h, tb + ".ff.net.2.bias", C);
   if (chain) {
@@ -239,6 +301,7 @@ Attn make_attn(hedit_unet* h, const std::string& pre, int C) {
   } else {
     a.pout = linp(h, pre + ".proj_out.weight", C, C);
   }
+  grad_lin(h, C, C, 1.f, &a.pout_t, chain ? &a.pout : nullptr);
   a.pout_b = f32p(h, pre + ".proj_out.bias", C);
   return a;
 }
@@ -903,10 +966,11 @@ int forward_impl(hedit_unet* h, const float* x, float t, const float* ctx, int B
 
 }  // namespace
 
-// =============================================================================== C ABI
-extern "C" {
+#include "unetgrad.h"
 
-int hedit_unet_create(const hedit_unet_cfg* cfg, hedit_unet** out) try {
+// =============================================================================== C ABI
+// grad: attach the input-gradient twins (hedit_unet_create_grad); without it, exactly the forward-only handle
+static int create_impl(const hedit_unet_cfg* cfg, hedit_unet** out, bool grad) {
   ARG_CHECK(cfg && out, "null");
   ARG_CHECK(cfg->n_levels >= 2 && cfg->n_levels <= HEDIT_MAX_LEVELS, "n_levels");
   ARG_CHECK(cfg->in_channels <= 8 && cfg->out_channels <= 4, "in/out channels");
@@ -918,8 +982,10 @@ int hedit_unet_create(const hedit_unet_cfg* cfg, hedit_unet** out) try {
     ARG_CHECK(d == 32 || d == 40 || d == 64 || d == 80 || d == 160, "head dim must be one of 32,40,64,80,160");
   }
   TRY(gemm_prepare());
+  if (grad) ARG_CHECK(cfg->in_channels <= 4, "the input-gradient pass needs in_channels <= 4");
   hedit_unet* h = new hedit_unet();
   h->cfg = *cfg;
+  h->grad = grad;
   const int* ch = cfg->block_out_channels;
   const int L = cfg->layers_per_block, n = cfg->n_levels;
   h->temb_dim = ch[0] * 4;
@@ -941,6 +1007,10 @@ int hedit_unet_create(const hedit_unet_cfg* cfg, hedit_unet** out) try {
   {
     Slot& cs = h->slots.back();
     cs.ndim = 4; cs.dims[0] = ch[0]; cs.dims[1] = cfg->in_channels; cs.dims[2] = 3; cs.dims[3] = 3;
+  }
+  if (grad) {   // [4][9][ch0], rows beyond in_channels zero: the N = 4 route of the head convolution
+    h->conv_in_t = add_extra<bf16_t>(h, 11, nullptr, (size_t)4 * 9 * ch[0], ch[0], cfg->in_channels);
+    if (h->conv_in_t && hipMemset(h->conv_in_t, 0, (size_t)4 * 9 * ch[0] * sizeof(bf16_t)) != hipSuccess) h->conv_in_t = nullptr;
   }
   h->conv_in_b = f32p(h, "conv_in.bias", ch[0]);
   h->te1_w = linp(h, "time_embedding.linear_1.weight", h->temb_dim, ch[0]);
@@ -972,6 +1042,7 @@ int hedit_unet_create(const hedit_unet_cfg* cfg, hedit_unet** out) try {
     if (i != n - 1) {
       b.has_sampler = true;
       b.samp_w = conv3p(h, pre + ".downsamplers.0.conv.weight", outc, outc);
+      if (grad) b.samp_t = add_extra<bf16_t>(h, 12, nullptr, (size_t)outc * outc * 9, outc, outc);
       b.samp_b = f32p(h, pre + ".downsamplers.0.conv.bias", outc);
     }
     h->down.push_back(b);
@@ -997,6 +1068,7 @@ int hedit_unet_create(const hedit_unet_cfg* cfg, hedit_unet** out) try {
     if (i != n - 1) {
       b.has_sampler = true;
       b.samp_w = conv3p(h, pre + ".upsamplers.0.conv.weight", outc, outc);
+      if (grad) b.samp_t = add_extra<bf16_t>(h, 11, nullptr, (size_t)outc * outc * 9, outc, outc);
       b.samp_b = f32p(h, pre + ".upsamplers.0.conv.bias", outc);
     }
     h->up.push_back(b);
@@ -1004,6 +1076,11 @@ int hedit_unet_create(const hedit_unet_cfg* cfg, hedit_unet** out) try {
   h->gn_out_g = f32p(h, "conv_norm_out.weight", ch[0]);
   h->gn_out_b = f32p(h, "conv_norm_out.bias", ch[0]);
   h->conv_out_w = conv3p(h, "conv_out.weight", cfg->out_channels, ch[0]);
+  if (grad) {
+    h->conv_out_t = add_extra<float>(h, 13, nullptr, (size_t)cfg->out_channels * ch[0] * 9, cfg->out_channels, ch[0]);
+    h->zero_bias = dalloc<float>(h, ch[0]);
+    if (h->zero_bias && hipMemset(h->zero_bias, 0, ch[0] * sizeof(float)) != hipSuccess) h->zero_bias = nullptr;
+  }
   h->conv_out_b = f32p(h, "conv_out.bias", cfg->out_channels);
 
   {
@@ -1028,14 +1105,28 @@ int hedit_unet_create(const hedit_unet_cfg* cfg, hedit_unet** out) try {
   }
   for (void* p : h->owned)
     if (!p) { hedit_set_error("hipMalloc failed while creating the UNet"); return HEDIT_ERR_HIP; }
-  for (auto& s : h->slots)
+  for (auto& s : h->slots) {
     if (!s.dst) { hedit_set_error("hipMalloc failed for " + s.name); return HEDIT_ERR_HIP; }
+    for (auto& e : s.extra)
+      if (!e.dst) { hedit_set_error("hipMalloc failed for the gradient twin of " + s.name); return HEDIT_ERR_HIP; }
+  }
   *out = h;
   return HEDIT_OK;
+}
+
+extern "C" {
+
+int hedit_unet_create(const hedit_unet_cfg* cfg, hedit_unet** out) try {
+  return create_impl(cfg, out, false);
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_unet_create_grad(const hedit_unet_cfg* cfg, hedit_unet** out) try {
+  return create_impl(cfg, out, true);
 } catch (...) { return hedit_abi_catch(); }
 
 void hedit_unet_destroy(hedit_unet* h) try {
   if (!h) return;
+  drop_tape(h);
   for (void* p : h->owned) (void)hipFree(p);
   for (hipEvent_t e : h->prof_pool) (void)hipEventDestroy(e);
   delete h;
@@ -1091,6 +1182,15 @@ int hedit_unet_load(hedit_unet* h, const char* name, const float* w, size_t nume
     TRY(lin_chain_pack_launch(w, s.which, s.scale, s.lay, reinterpret_cast<bf16_t*>(s.dst), st));
   } else {
     TRY(pack_conv3x3_launch(w, reinterpret_cast<bf16_t*>(s.dst), s.O, s.I, st));
+  }
+  for (const Slot::Extra& e : s.extra) {
+    bf16_t* d16 = reinterpret_cast<bf16_t*>(e.dst);
+    if (e.kind == 0) HIP_TRY(hipMemcpyAsync(e.dst, w, numel * sizeof(float), hipMemcpyDeviceToDevice, st));
+    else if (e.kind == 1) TRY(pack_linear_launch(w, d16, (long)numel, e.scale, st));
+    else if (e.kind == 10) TRY(pack_linear_t_launch(w, d16, e.O, e.I, st, e.scale));
+    else if (e.kind == 11) TRY(pack_conv3x3_dgrad_launch(w, d16, e.O, e.I, st));
+    else if (e.kind == 12) TRY(pack_conv3x3_s2_dgrad_launch(w, d16, e.O, e.I, st));
+    else TRY(flip_oihw_launch(w, reinterpret_cast<float*>(e.dst), e.O, e.I, 3, st));
   }
   s.loaded = true;
   return HEDIT_OK;
@@ -1167,6 +1267,69 @@ int hedit_unet_forward_shared(hedit_unet* h, const float* x, int D, const int* r
   }
   return forward_impl(h, x, t, ctx, B, height, width, plan, eps_out, workspace, workspace_bytes,
                       reinterpret_cast<hipStream_t>(stream), false, nullptr, D, &map);
+} catch (...) { return hedit_abi_catch(); }
+
+// ---- input gradient (unetgrad.h)
+size_t hedit_unet_grad_workspace_bytes(hedit_unet* h, int B, int height, int width) try {
+  if (!h || !h->grad || check_grad_shape(h, B, height, width) != HEDIT_OK) return 0;
+  GradTape T;
+  tape_init(T, h, B, height, width, nullptr, 0, nullptr, true);
+  float dummy = 0.f;   // never dereferenced in the dry run
+  int rc = forward_keep_impl(h, T, nullptr, 0.f, nullptr, nullptr);
+  if (rc == HEDIT_OK) rc = backward_impl(h, T, &dummy, &dummy);
+  return rc == HEDIT_OK ? T.f.ar.peak + 4096 : 0;
+} catch (...) { (void)hedit_abi_catch(); return 0; }
+
+int hedit_unet_forward_keep(hedit_unet* h, const float* x, float t, const float* ctx, int B, int height, int width, float* eps,
+                            void* workspace, size_t workspace_bytes, void* stream) try {
+  ARG_CHECK(h && x && ctx && eps && workspace, "null");
+  TRY(check_grad_shape(h, B, height, width));
+  TRY(check_grad_handle(h, "hedit_unet_forward_keep"));
+  drop_tape(h);
+  GradTape* T = new GradTape();
+  tape_init(*T, h, B, height, width, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false);
+  const int rc = forward_keep_impl(h, *T, x, t, ctx, eps);
+  if (rc != HEDIT_OK) {
+    delete T;
+    return rc;
+  }
+  h->tape = T;
+  h->tape_free = [](void* p) { delete reinterpret_cast<GradTape*>(p); };
+  return HEDIT_OK;
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_unet_backward(hedit_unet* h, const float* d_eps, float* d_x, void* workspace, void* stream) try {
+  ARG_CHECK(h && d_eps && d_x && workspace, "null");
+  TRY(check_grad_handle(h, "hedit_unet_backward"));
+  if (!h->tape) {
+    hedit_set_error("hedit_unet_backward: no forward is being kept (call hedit_unet_forward_keep first)");
+    return HEDIT_ERR_STATE;
+  }
+  GradTape* T = reinterpret_cast<GradTape*>(h->tape);
+  if (T->ws != workspace) {
+    hedit_set_error("hedit_unet_backward: not the workspace the kept forward ran in");
+    return HEDIT_ERR_ARG;
+  }
+  T->f.st = reinterpret_cast<hipStream_t>(stream);
+  const int rc = backward_impl(h, *T, d_eps, d_x);
+  if (rc != HEDIT_OK) drop_tape(h);   // a pass that stopped half way leaves temporaries in the arena
+  return rc;
+} catch (...) { return hedit_abi_catch(); }
+
+void hedit_unet_release(hedit_unet* h) try {
+  if (h) drop_tape(h);
+} catch (...) { (void)hedit_abi_catch(); }
+
+int hedit_unet_vjp(hedit_unet* h, const float* x, float t, const float* ctx, const float* d_eps, int B, int height, int width,
+                   float* d_x, float* eps, void* workspace, size_t workspace_bytes, void* stream) try {
+  ARG_CHECK(h && x && ctx && d_eps && d_x && eps && workspace, "null");
+  TRY(check_grad_shape(h, B, height, width));
+  TRY(check_grad_handle(h, "hedit_unet_vjp"));
+  drop_tape(h);
+  GradTape T;
+  tape_init(T, h, B, height, width, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false);
+  TRY(forward_keep_impl(h, T, x, t, ctx, eps));
+  return backward_impl(h, T, d_eps, d_x);
 } catch (...) { return hedit_abi_catch(); }
 
 int hedit_prof_enable(hedit_unet* h, int on, int max_records) try {

@@ -84,6 +84,14 @@ _SIGS = {
                                      C.c_void_p]),
     "hedit_unet_forward_shared": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_void_p, C.c_int,
                                             C.c_int, C.c_int, C.POINTER(P2PPlan), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hedit_unet_create_grad": (C.c_int, [C.POINTER(UnetCfg), C.POINTER(C.c_void_p)]),
+    "hedit_unet_grad_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "hedit_unet_forward_keep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hedit_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hedit_unet_release": (None, [C.c_void_p]),
+    "hedit_unet_vjp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hedit_unet_set_attn_hook": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "hedit_unet_num_store_layers": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "hedit_unet_store_layer_info": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
@@ -312,6 +320,14 @@ _SIGS = {
     "hedit_k_slice_add": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "hedit_k_pack_linear_t": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "hedit_k_flip_oihw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "hedit_k_attn_bwd_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "hedit_k_attn_bwd": (C.c_int, [C.c_void_p, C.c_int] * 6 + [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
+    "hedit_k_cross_attn_bwd_q": (C.c_int, [C.c_void_p, C.c_int] * 6 + [C.c_int] * 4 + [C.c_void_p]),
+    "hedit_k_layernorm_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_float, C.c_void_p]),
+    "hedit_k_groupnorm_bwd_any": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
+    "hedit_k_geglu_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "hedit_k_conv3x3_s2_dgrad_pad1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

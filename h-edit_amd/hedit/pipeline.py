@@ -18,17 +18,19 @@ class HEditPipeline:
         self.vae = vae
 
     @classmethod
-    def from_random(cls, config=None, seed=0, device="cuda:0", text_layers=12, vae_config=None, with_vae=False, native_text=False):
+    def from_random(cls, config=None, seed=0, device="cuda:0", text_layers=12, vae_config=None, with_vae=False, native_text=False,
+                    grad=False):
         """SD-1.x-shaped pipeline with seeded synthetic weights (no checkpoints offline).
         ``with_vae`` adds the image autoencoder (hedit.vae.AutoencoderKL, SD-1.x shape unless
         ``vae_config`` says otherwise).  ``native_text``: the stand-in's weights run on the native prompt encoder
-        (hedit.text.NativeClipText, head dimension 64: ``heads = width // 64``) instead of the torch module."""
+        (hedit.text.NativeClipText, head dimension 64: ``heads = width // 64``) instead of the torch module.
+        ``grad``: the UNet also carries its input-gradient weights (UNet2DConditionModel(grad=True))."""
         cfg = dict(SD15_CONFIG)
         cfg.update(config or {})
         dim = cfg["cross_attention_dim"]
         if native_text and dim % 64:
             raise ValueError(f"native_text: cross_attention_dim {dim} is not a multiple of the head dimension 64")
-        unet = UNet2DConditionModel(cfg, device=device)
+        unet = UNet2DConditionModel(cfg, device=device, grad=grad)
         unet.init_random(seed)
         heads = 12 if dim % 12 == 0 else 4
         if native_text:
@@ -45,7 +47,7 @@ class HEditPipeline:
         return cls(unet, DDIMScheduler(), WordTokenizer(stable_ids=True), enc, vae, device)
 
     @classmethod
-    def from_pretrained(cls, path, device="cuda:0", tokenizer=None, text_encoder=None, native_text=False):
+    def from_pretrained(cls, path, device="cuda:0", tokenizer=None, text_encoder=None, native_text=False, grad=False):
         """Load a LOCAL Stable-Diffusion-1.x checkpoint directory in the diffusers layout (what the
         reference's ``StableDiffusionPipeline.from_pretrained(model_id)`` resolves to,
         text-guided/main_p2p.py:104-106).  The UNet and VAE run on the HIP executors; the CLIP
@@ -61,7 +63,7 @@ class HEditPipeline:
         # (RCCL over xGMI, hedit.dist.state_dict_from_rank0).  The small config.json files are read by every rank.
         from . import dist as HD
         ucfg = CK.read_config(os.path.join(path, "unet"))
-        unet = UNet2DConditionModel(CK.unet_config(ucfg), device=device)
+        unet = UNet2DConditionModel(CK.unet_config(ucfg), device=device, grad=grad)
         usd = HD.state_dict_from_rank0(lambda: CK.read_component(os.path.join(path, "unet"))[1], unet.param_shapes, device=device,
                                        bf16_names=unet.bf16_exact)
         unet.load_state_dict(usd)

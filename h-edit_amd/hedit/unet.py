@@ -15,6 +15,11 @@ p2p/ptp_utils.py:98-106, p2p/ptp_classes.py:91-108) is served by the hook path o
 (``hedit_unet_set_attn_hook``): every attention layer materialises its probabilities, the controller
 sees and may rewrite them in place, the executor multiplies what comes back with V.  Slow (fp32
 probabilities through HBM), same protocol.
+
+``UNet2DConditionModel(config, device, grad=True)`` also carries the input-gradient weights (hedit_unet_create_grad):
+whenever grad mode is on and ``sample.requires_grad``, a PLAIN pass (``use_controller=False`` or no controller registered,
+no attention editor) is an autograd node whose backward is the executor's input-gradient pass -- what Noise Map Guidance
+differentiates (text-guided/inversion/p2p_baselines.py:251-268).  The gradient is with respect to the sample only.
 """
 import ctypes as C
 import hashlib
@@ -75,8 +80,35 @@ def random_state_dict(param_shapes, seed=0):
     return sd
 
 
+class _EpsGrad(torch.autograd.Function):
+    """eps = unet(sample, t, ctx) with the forward's tape kept in the model's gradient workspace; backward = the executor's
+    vector-Jacobian product.  The tape stays until the model's next call, so ``retain_graph=True`` and a second backward
+    work; a backward after the model has run again is an error, not another forward's gradient (the ticket check of
+    hedit/diffusion/diffusion.py)."""
+
+    @staticmethod
+    def forward(ctx, sample, model, t, enc):
+        ctx.model = model
+        ctx.ticket, eps = model._keep(sample.detach(), t, enc)
+        ctx.shape = sample.shape
+        return eps
+
+    @staticmethod
+    def backward(ctx, g):
+        m = ctx.model
+        if m._ticket != ctx.ticket:
+            raise RuntimeError("hedit.UNet2DConditionModel: the kept forward of this graph was dropped by a later model call")
+        g = g.detach().to(dtype=torch.float32).contiguous()
+        dx = torch.empty(ctx.shape, dtype=torch.float32, device=m.device)
+        with torch.cuda.device(m.device):
+            _lib.check(m._lib.hedit_unet_backward(m._h, _lib.ptr(g), _lib.ptr(dx), _lib.ptr(m._gws), _lib.cur_stream()))
+        return dx, None, None, None
+
+
 class UNet2DConditionModel:
-    def __init__(self, config=None, device="cuda:0"):
+    _tickets = 0      # kept forwards so far, over all models: a ticket is never reused
+
+    def __init__(self, config=None, device="cuda:0", grad=False):
         cfg = dict(SD15_CONFIG)
         cfg.update(config or {})
         self.config = cfg
@@ -101,8 +133,12 @@ class UNet2DConditionModel:
         self._cfg_struct = c
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.hedit_unet_create(C.byref(c), C.byref(h)))
+            create = self._lib.hedit_unet_create_grad if grad else self._lib.hedit_unet_create
+            _lib.check(create(C.byref(c), C.byref(h)))
         self._h = h
+        self.grad = bool(grad)
+        self._ticket = 0          # identifies the kept forward; 0 = none
+        self._gws = None          # the tape's workspace (hedit_unet_grad_workspace_bytes)
         self.param_shapes = {}
         self.bf16_exact = set()       # parameters the executor keeps as unscaled bf16 copies (hedit.dist sends those as bf16)
         nd, dims = C.c_int(), (C.c_int * 4)()
@@ -293,6 +329,32 @@ class UNet2DConditionModel:
             _lib.cur_stream()))
         return out
 
+    # ---------------------------------------------------------------- input gradient
+    def _release(self):
+        if self._ticket:
+            self._lib.hedit_unet_release(self._h)
+            self._ticket = 0
+
+    def _keep(self, sample, t, ctx):
+        """plain forward that leaves its tape in the gradient workspace -> (the ticket a backward must present, eps)"""
+        sample, ctx = sample.contiguous(), ctx.detach().contiguous()
+        B, _, H, W = sample.shape
+        if ctx.shape != (B, 77, self.config["cross_attention_dim"]):
+            raise ValueError(f"encoder_hidden_states must be ({B}, 77, {self.config['cross_attention_dim']}), got {tuple(ctx.shape)}")
+        need = self._lib.hedit_unet_grad_workspace_bytes(self._h, B, H, W)
+        if need == 0:
+            raise _lib.HipError("gradient workspace planning failed: " + self._lib.hedit_last_error().decode())
+        if self._gws is None or self._gws.numel() < need:
+            self._gws = None
+            self._gws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        eps = torch.empty(B, self.config["out_channels"], H, W, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.hedit_unet_forward_keep(self._h, _lib.ptr(sample), C.c_float(float(t)), _lib.ptr(ctx), B, H, W,
+                                                         _lib.ptr(eps), _lib.ptr(self._gws), self._gws.numel(), _lib.cur_stream()))
+        UNet2DConditionModel._tickets += 1
+        self._ticket = UNet2DConditionModel._tickets
+        return self._ticket, eps
+
     _HOOK_T = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p)
 
     def forward_hooked(self, sample, t, ctx, controller, save_attn=True, out=None):
@@ -350,6 +412,17 @@ class UNet2DConditionModel:
             # an attention editor registered on the UNet (MasaCtrl: regiter_attention_editor_diffusers; Plug-and-Play:
             # register_attention_control_efficient / register_conv_control_efficient)
             controller = getattr(self, "_attention_editor", None)
+        if self.grad:
+            self._release()
+            if torch.is_grad_enabled() and encoder_hidden_states.requires_grad:
+                raise NotImplementedError("the gradient with respect to encoder_hidden_states (null-text inversion) is not "
+                                          "implemented: the input-gradient pass differentiates the sample only")
+            if torch.is_grad_enabled() and sample.requires_grad:
+                if controller is not None:
+                    what = "an attention editor" if controller is getattr(self, "_attention_editor", None) else "a registered controller"
+                    raise NotImplementedError(f"{what} is in the way: the input-gradient pass differentiates the plain network "
+                                              "only (pass cross_attention_kwargs={'use_controller': False, 'use_editor': False})")
+                return UNetOutput(sample=_EpsGrad.apply(sample, self, t, ctx))
         from .p2p.ptp_classes import runs_in_python
         if runs_in_python(controller):
             return UNetOutput(sample=self.forward_hooked(sample, t, ctx, controller, save_attn))

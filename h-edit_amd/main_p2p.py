@@ -85,11 +85,11 @@ def load_model(args, device):
             from hedit.vae import TINY_VAE_CONFIG
             vcfg = dict(TINY_VAE_CONFIG)
             vcfg.update(block_out_channels=(64, 64, 128, 128))          # f = 8 like SD
-            return HEditPipeline.from_random(TINY_CONFIG, seed=args.seed, device=device, text_layers=2, vae_config=vcfg, native_text=getattr(args, "native_text", False))
-        return HEditPipeline.from_random(seed=args.seed, device=device, with_vae=True, native_text=getattr(args, "native_text", False))
+            return HEditPipeline.from_random(TINY_CONFIG, seed=args.seed, device=device, text_layers=2, vae_config=vcfg, native_text=getattr(args, "native_text", False), grad=getattr(args, "unet_grad", False))
+        return HEditPipeline.from_random(seed=args.seed, device=device, with_vae=True, native_text=getattr(args, "native_text", False), grad=getattr(args, "unet_grad", False))
     if not args.model_path:
         raise SystemExit("give --model_path DIR (local diffusers-layout checkpoint) or --random_init")
-    return HEditPipeline.from_pretrained(args.model_path, device=device, native_text=getattr(args, "native_text", False))
+    return HEditPipeline.from_pretrained(args.model_path, device=device, native_text=getattr(args, "native_text", False), grad=getattr(args, "unet_grad", False))
 
 
 def edit_group(args, model, entries, scale, size, device):

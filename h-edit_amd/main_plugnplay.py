@@ -79,7 +79,7 @@ def load_pnp_model(args, device):
         ucfg["sample_size"] = 64
         vcfg = dict(TINY_VAE_CONFIG)
         vcfg.update(block_out_channels=(64, 64, 128))                 # f = 4: 256 x 256 images
-        return HEditPipeline.from_random(ucfg, seed=args.seed, device=device, text_layers=2, vae_config=vcfg, native_text=getattr(args, "native_text", False))
+        return HEditPipeline.from_random(ucfg, seed=args.seed, device=device, text_layers=2, vae_config=vcfg, native_text=getattr(args, "native_text", False), grad=getattr(args, "unet_grad", False))
     return load_model(args, device)
 
 

@@ -167,6 +167,28 @@ int hedit_unet_num_store_layers(const hedit_unet* h, int height, int width);
 int hedit_unet_store_layer_info(const hedit_unet* h, int height, int width, int i, int* tokens,
                                 int* place /*0 down,1 mid,2 up*/);
 
+/* Input gradient of the network: d_x = (d eps / d x)^T d_eps of a PLAIN pass (no plan, no hook) -- what Noise Map Guidance
+ * differentiates (text-guided/inversion/p2p_baselines.py:195-293).  With respect to x only: nothing for ctx, t or the weights.
+ * hedit_unet_create_grad: hedit_unet_create (same parameters, same names) whose hedit_unet_load also fills the input-gradient
+ *   twins (transposed linear weights, dgrad-packed convolutions) and, at the width the forward-only handle runs as chain
+ *   kernels, the unfused weights.  in_channels <= 4.  Such a handle serves hedit_unet_forward as before.
+ * hedit_unet_forward_keep: the network through the unfused kernels with every block recorded inside `workspace`
+ *   (hedit_unet_grad_workspace_bytes, which also covers the backward's temporaries); eps is within the forward's tolerance of
+ *   hedit_unet_forward's, not its bits.  The tape lives until the next forward_keep / vjp / release on the handle; the
+ *   workspace must stay untouched meanwhile.
+ * hedit_unet_backward: one pass over the tape, which it leaves intact (any number of cotangents per forward; the same bits
+ *   each time).  d_eps fp32 [B][Cout][H][W] -> d_x fp32 [B][Cin][H][W].  Batch rows are the bits of single calls.
+ * hedit_unet_vjp: both in one call, nothing kept.
+ * HEDIT_ERR_STATE: a forward-only handle, a backward without a tape, or a set attention hook. */
+int hedit_unet_create_grad(const hedit_unet_cfg* cfg, hedit_unet** out);
+size_t hedit_unet_grad_workspace_bytes(hedit_unet* h, int B, int height, int width);
+int hedit_unet_forward_keep(hedit_unet* h, const float* x, float t, const float* ctx, int B, int height, int width, float* eps,
+                            void* workspace, size_t workspace_bytes, void* stream);
+int hedit_unet_backward(hedit_unet* h, const float* d_eps, float* d_x, void* workspace, void* stream);
+void hedit_unet_release(hedit_unet* h);
+int hedit_unet_vjp(hedit_unet* h, const float* x, float t, const float* ctx, const float* d_eps, int B, int height, int width,
+                   float* d_x, float* eps, void* workspace, size_t workspace_bytes, void* stream);
+
 /* Sampled launch timing for bench.py's roofline: while enabled, every kernel launch of
  * hedit_unet_forward is bracketed by a HIP event pair on the launch stream (up to max_records
  * launches).  kind: 0 conv3x3 GEMM, 1 linear/1x1 GEMM, 2 self-attention, 3 cross-attention,
@@ -452,6 +474,37 @@ int hedit_k_flip_oihw(const float* w_oihw, float* out, int O, int I, int k, void
 int hedit_k_pack_conv3x3_s2_dgrad(const float* w_oihw, void* out, int O, int I, void* stream);
 int hedit_k_conv3x3_s2_dgrad(const void* dy, const void* w_packed, void* dx, int B, int Hin, int Win, int O, int I, void* stream);
 int hedit_k_slice_add(const void* src, int ld, int off, int c, void* dst, int64_t rows, int accumulate, void* stream);
+/* The pieces the SD UNet's input-gradient pass adds to those (tests/test_gpu_unet_grad.py).  All 16-bit tensors in the
+ * storage format of the build.
+ * hedit_k_attn_bwd: multi-head self-attention backward without a T x T tensor and without atomics (csrc/attnbwd.hip).
+ *   q, k as hedit_k_self_attn takes them ([B*N][ld], head h at column h*d, q pre-scaled by scale*log2(e)); v ROW-MAJOR
+ *   [B*N][ldv] (not V^T); o = the forward's output and dout = its gradient, [B*N][ld].  dq [B*N][lddq] is the gradient with
+ *   respect to the PRE-SCALED q; dk, dv are dense [B*N][heads*d].  ws of hedit_k_attn_bwd_ws_bytes.  d in {32, 40, 64, 80,
+ *   160}, N % 64 == 0, every row stride a multiple of 8 and >= heads*d.
+ * hedit_k_cross_attn_bwd_q: the query gradient of the attention over the 77 context rows (k, v [B*80][ld]; rows 77 .. 79 of an
+ *   image are never read); the context is not differentiated.
+ * hedit_k_layernorm_bwd: dx = d LayerNorm(x) / dx applied to dy (+ add, or NULL, summed in fp32 with one rounding); mean and
+ *   rstd recomputed from x in fp32.  C % 8 == 0, C <= 1536.
+ * hedit_k_geglu_bwd: x = [value | gate] [rows][2 inner] as hedit_k_geglu takes it, dy [rows][inner] the gradient of
+ *   value * gelu(gate) -> dx [rows][2 inner], with the analytic derivative of the exact (erf) GELU.  inner % 8 == 0.
+ * hedit_k_conv3x3_s2_dgrad_pad1: hedit_k_conv3x3_s2_dgrad for padding 1 all round (hedit_k_gemm mode 2 without asym): the
+ *   parities mirrored, 1 / 2 / 2 / 4 taps; the same packed weight and the same conditions.
+ * hedit_k_groupnorm_bwd_any: hedit_k_groupnorm_bwd for the widths of skip concatenations, as the executors call it: C / 8 need
+ *   not divide 256 (the spare threads idle), and rows of more than 2048 channels (C / 8 in 257 .. 512: SD-1.5's 2560) run
+ *   512-thread blocks.  Same arithmetic; the same ws size function. */
+size_t hedit_k_attn_bwd_ws_bytes(int B, int N, int heads);
+int hedit_k_attn_bwd(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o, int ldo,
+                     const void* dout, int lddo, void* dq, int lddq, void* dk, void* dv, int B, int N, int heads, int d,
+                     void* ws, void* stream);
+int hedit_k_cross_attn_bwd_q(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o, int ldo,
+                             const void* dout, int lddo, void* dq, int lddq, int B, int N, int heads, int d, void* stream);
+int hedit_k_layernorm_bwd(const void* x, const void* dy, const void* add, void* dx, const float* gamma, int64_t rows, int C,
+                          float eps, void* stream);
+int hedit_k_groupnorm_bwd_any(const void* x, const void* dy, const void* add, void* dx, const float* gamma, const float* beta,
+                              const float* stats, int B, int HW, int C, int G, int silu, void* ws, void* stream);
+int hedit_k_geglu_bwd(const void* x, const void* dy, void* dx, int64_t rows, int inner, void* stream);
+int hedit_k_conv3x3_s2_dgrad_pad1(const void* dy, const void* w_packed, void* dx, int B, int Hin, int Win, int O, int I,
+                                  void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Pixel-space DDPM UNet of the face-swapping task: `Model.forward(x, t)` of
