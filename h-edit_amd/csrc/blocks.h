@@ -83,6 +83,11 @@ float* vec(ParamStore* h, const std::string& name, int n) {
   add_slot(h, name, 0, d, n, 0, 0, 1, n, 1, 1, 1);
   return d;
 }
+float* mat(ParamStore* h, const std::string& name, int O, int I) {   // a [O][I] matrix kept fp32 (packed by the executor's finalize)
+  float* d = dalloc<float>(h, (size_t)O * I);
+  add_slot(h, name, 0, d, (size_t)O * I, O, I, 2, O, I, 1, 1);
+  return d;
+}
 float* f32conv(ParamStore* h, const std::string& name, int O, int I, int k) {   // kept fp32, torch layout
   float* d = dalloc<float>(h, (size_t)O * I * k * k);
   add_slot(h, name, 0, d, (size_t)O * I * k * k, O, I, 4, O, I, k, k);
@@ -582,6 +587,18 @@ inline int store_missing(const ParamStore* h) {
   int m = 0;
   for (auto& s : h->slots) m += s.loaded ? 0 : 1;
   return m;
+}
+// the parameter table as the *_num_params / *_param_name / *_param_shape entries of every handle report it
+inline int store_num_params(const ParamStore* h) { return h ? (int)h->slots.size() : 0; }
+inline const char* store_param_name(const ParamStore* h, int i) {
+  if (!h || i < 0 || i >= (int)h->slots.size()) return nullptr;
+  return h->slots[i].name.c_str();
+}
+inline int store_param_shape(const ParamStore* h, int i, int* ndim, int* dims4) {
+  ARG_CHECK(h && ndim && dims4 && i >= 0 && i < (int)h->slots.size(), "param index");
+  *ndim = h->slots[i].ndim;
+  for (int k = 0; k < 4; ++k) dims4[k] = h->slots[i].dims[k];
+  return HEDIT_OK;
 }
 inline void store_free(ParamStore* h) {
   for (void* p : h->owned) if (p) (void)hipFree(p);

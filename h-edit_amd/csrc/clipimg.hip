@@ -9,63 +9,14 @@
 // the bytes of single calls.  The output is fp32 and nothing here reads the storage type, so both builds give the same bits.
 // Parameters by the OpenAI CLIP state_dict names (`visual.conv1.weight` ... `visual.ln_post.weight`, `visual.proj`).
 //
-// The small kernels vit.hip / text.hip also have (patches, tokens, LayerNorm forward, out = res + raw + bias, the row
-// gather) are restated here rather than shared: neither file is touched.  What is new is the attention kernel: vit.hip keeps
-// all keys and values of an (image, head) in LDS, which ends at 200 tokens; this one walks them in tiles.
-#include "pnet.h"
+// The kernels every encoder runs (patches, tokens, LayerNorm forward, out = res + raw + bias, the row gather) are those of
+// encoder.hip and the block forward is encoder.h's.  What is this file's own is the attention kernel: vit.hip keeps all keys
+// and values of an (image, head) in LDS, which ends at 200 tokens; this one walks them in tiles.
+#include "encoder.h"
 
 namespace {
 
 constexpr float LN_EPS = 1e-5f;
-
-// img [B][3][R][R] -> X [B*P*P][3*p*p], column = (c, ky, kx): conv1 with kernel = stride = p is a linear map
-__global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__ img, float* __restrict__ X, int B, int R, int p) {
-  const int P = R / p, K = 3 * p * p;
-  const long total = (long)B * P * P * K;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int k = (int)(i % K);
-    const long row = i / K;
-    const int b = (int)(row / (P * P)), pr = (int)(row % (P * P));
-    const int c = k / (p * p), ky = (k / p) % p, kx = k % p;
-    X[i] = img[(((long)b * 3 + c) * R + (pr / P) * p + ky) * R + (pr % P) * p + kx];
-  }
-}
-// T0[b][0] = cls + pos[0]; T0[b][1+l] = E[b][l] + pos[1+l]
-__global__ __launch_bounds__(256) void tokens_kernel(const float* __restrict__ E, const float* __restrict__ cls, const float* __restrict__ pos,
-                                                     float* __restrict__ T, int B, int L, int W) {
-  const long total = (long)B * L * W;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int w = (int)(i % W);
-    const long row = i / W;
-    const int b = (int)(row / L), l = (int)(row % L);
-    T[i] = (l == 0 ? cls[w] : E[((long)b * (L - 1) + l - 1) * W + w]) + pos[(long)l * W + w];
-  }
-}
-// R[b] = T[b][0]: the class rows
-__global__ __launch_bounds__(256) void class_rows_kernel(const float* __restrict__ T, float* __restrict__ R, int B, int L, int W) {
-  const long total = (long)B * W;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) R[i] = T[(i / W) * L * W + i % W];
-}
-// LayerNorm over W, one wave per row (the arithmetic of vit.hip's ln_fwd_kernel; no statistics are kept)
-__global__ __launch_bounds__(256) void ln_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b,
-                                                 float* __restrict__ y, long rows, int W) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* xr = x + row * W;
-  float s = 0.f;
-  for (int i = lane; i < W; i += 64) s += xr[i];
-  const float mean = wave_sum(s) / (float)W;
-  float q = 0.f;
-  for (int i = lane; i < W; i += 64) { const float d = xr[i] - mean; q += d * d; }
-  const float rstd = rsqrtf(wave_sum(q) / (float)W + LN_EPS);
-  for (int i = lane; i < W; i += 64) y[row * W + i] = (xr[i] - mean) * rstd * g[i] + b[i];
-}
-// out = res + raw + bias
-__global__ __launch_bounds__(256) void add_bias_res_kernel(const float* __restrict__ raw, const float* __restrict__ bias, const float* __restrict__ res,
-                                                           float* __restrict__ out, long total, int W) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) out[i] = res[i] + raw[i] + bias[i % W];
-}
 
 // ---- bidirectional attention over the L tokens of one image, head dimension 64, fp32, any L: the keys and values of an
 // (image, head) pass through LDS in tiles of TK = 128 rows and the softmax is carried across the tiles (running maximum m,
@@ -195,26 +146,6 @@ __global__ __launch_bounds__(256, 2) void tiled_attn_kernel(const float* __restr
   }
 }
 
-struct CBlock {
-  float *ln1g, *ln1b, *ln2g, *ln2b, *win, *bin, *wo, *bo, *wfc, *bfc, *wp, *bp;
-  PConv in, out, fc, proj;
-};
-
-inline dim3 egrid(long total) { return dim3(ew_grid(total)); }
-
-// forward-only packed weight of out = x . w^T, w [O][I] (make_pconv of pnet.h also builds the input-gradient twin, which
-// nothing here would read: 0.6 GB at ViT-L/14).  transposed: w is [O][I] and the product is x [M][O] . w -> [M][I].
-int pack_fwd(ParamStore* h, PConv& c, const float* w, int O, int I, bool transposed, hipStream_t st) {
-  c.O = O; c.I = I; c.k = 1;
-  c.rows_f = (O + 3) / 4 * 4;
-  c.rows_b = (I + 3) / 4 * 4;
-  bf16_t*& dst = transposed ? c.wb : c.wf;
-  const int rows = transposed ? c.rows_b : c.rows_f, Cin = transposed ? O : I;
-  if (!dst) dst = dalloc<bf16_t>(h, (size_t)rows * split_kp(Cin));
-  if (!dst) { hedit_set_error("hipMalloc failed for a packed weight"); return HEDIT_ERR_HIP; }
-  return pack_split3_w_launch(w, nullptr, dst, O, I, 1, transposed ? 1 : 0, split_cs(Cin), split_kp(Cin), rows, 0, 0, st);
-}
-
 }  // namespace
 
 struct hedit_clipimg : ParamStore {
@@ -224,87 +155,43 @@ struct hedit_clipimg : ParamStore {
   float *conv_w = nullptr, *cls = nullptr, *pos = nullptr, *lnpg = nullptr, *lnpb = nullptr, *lnog = nullptr, *lnob = nullptr,
         *proj_w = nullptr;
   PConv conv, proj;
-  std::vector<CBlock> blocks;
+  std::vector<EncBlock> blocks;
   bool finalized = false;
 };
 
 namespace {
 
-int ln(PF& f, const float* x, const float* g, const float* b, long rows, int W, float* y) {
-  if (!f.dry()) {
-    hipLaunchKernelGGL(ln_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, f.st, x, g, b, y, rows, W);
-    LAUNCH_CHECK();
-  }
-  return HEDIT_OK;
-}
-
-// the M rows of a [M][C] fp32 tensor as a split operand and through one linear layer: out raw [M][N]
-int lin(PF& f, const float* x, int C, int op, const float* q, const PConv& c, bool transposed, long M, float** out) {
-  bf16_t* A;
-  TRY(op_split(f, x, C, op, nullptr, q, 0, nullptr, 0, 1, 1, M, &A));
-  TRY(pgemm(f, A, c, transposed, 0, 1, 1, M, out));
-  f.ar.free(A);
-  return HEDIT_OK;
-}
-
 // img [B][3][R][R] (CLIP-normalised) -> out [B][embed_dim]
 int run(hedit_clipimg* h, const float* img, int B, float* out, void* ws, size_t ws_bytes, hipStream_t st, bool dry, size_t* peak) {
-  PF f{B, st, Arena{}};
-  f.ar.dry = dry;
-  f.ar.base = reinterpret_cast<char*>(ws);
-  f.ar.cap = ws_bytes;
+  PF f = make_pf(B, ws, ws_bytes, st, dry);
   const int W = h->cfg.width, L = h->L, R = h->cfg.input_resolution, p = h->cfg.patch_size, heads = h->cfg.heads, E = h->cfg.embed_dim;
   const int K0 = 3 * p * p;
   const long Mp = (long)B * (L - 1), M = (long)B * L;
   const float ascale = 1.0f / sqrtf((float)HD);
   float *X0, *Em, *T0, *T;
   TRY(palloc(f, &X0, (size_t)Mp * K0));
-  if (!dry) { hipLaunchKernelGGL(patchify_kernel, egrid(Mp * K0), dim3(256), 0, st, img, X0, B, R, p); LAUNCH_CHECK(); }
-  TRY(lin(f, X0, K0, P_COPY, nullptr, h->conv, false, Mp, &Em));
+  if (!dry) TRY(enc_patchify_launch(img, X0, B, R, p, 0, st));
+  TRY(lin(f, X0, K0, P_COPY, nullptr, nullptr, h->conv, false, Mp, &Em));
   f.ar.free(X0);
   TRY(palloc(f, &T0, (size_t)M * W));
-  if (!dry) { hipLaunchKernelGGL(tokens_kernel, egrid(M * W), dim3(256), 0, st, Em, h->cls, h->pos, T0, B, L, W); LAUNCH_CHECK(); }
+  if (!dry) TRY(enc_tokens_launch(Em, nullptr, h->cls, h->pos, T0, B, L, W, st));
   f.ar.free(Em);
   TRY(palloc(f, &T, (size_t)M * W));
-  TRY(ln(f, T0, h->lnpg, h->lnpb, M, W, T));
+  TRY(ln(f, T0, h->lnpg, h->lnpb, M, W, LN_EPS, T));
   f.ar.free(T0);
-  for (const CBlock& k : h->blocks) {
-    float *a, *qkv, *A, *raw, *Tmid, *m, *H, *Tn;
-    TRY(palloc(f, &a, (size_t)M * W));
-    TRY(ln(f, T, k.ln1g, k.ln1b, M, W, a));
-    TRY(lin(f, a, W, P_COPY, nullptr, k.in, false, M, &qkv));
-    f.ar.free(a);
-    TRY(palloc(f, &A, (size_t)M * W));
-    if (!dry) {
-      hipLaunchKernelGGL(tiled_attn_kernel, dim3(heads, B, attn_slices(L, h->slices)), dim3(256), ATTN_LDS, st, qkv, k.bin, A, L, W, ascale);
-      LAUNCH_CHECK();
-    }
-    f.ar.free(qkv);
-    TRY(lin(f, A, W, P_COPY, nullptr, k.out, false, M, &raw));
-    f.ar.free(A);
-    TRY(palloc(f, &Tmid, (size_t)M * W));
-    if (!dry) { hipLaunchKernelGGL(add_bias_res_kernel, egrid(M * W), dim3(256), 0, st, raw, k.bo, T, Tmid, M * W, W); LAUNCH_CHECK(); }
-    f.ar.free(raw);
-    f.ar.free(T);
-    TRY(palloc(f, &m, (size_t)M * W));
-    TRY(ln(f, Tmid, k.ln2g, k.ln2b, M, W, m));
-    TRY(lin(f, m, W, P_COPY, nullptr, k.fc, false, M, &H));
-    f.ar.free(m);
-    TRY(lin(f, H, 4 * W, P_QGELU, k.bfc, k.proj, false, M, &raw));      // QuickGELU(H + bias) as the operand op
-    f.ar.free(H);
-    TRY(palloc(f, &Tn, (size_t)M * W));
-    if (!dry) { hipLaunchKernelGGL(add_bias_res_kernel, egrid(M * W), dim3(256), 0, st, raw, k.bp, Tmid, Tn, M * W, W); LAUNCH_CHECK(); }
-    f.ar.free(raw);
-    f.ar.free(Tmid);
-    T = Tn;
-  }
+  auto attn = [&](const float* qkv, const float* bias, float* A) -> int {
+    hipLaunchKernelGGL(tiled_attn_kernel, dim3(heads, B, attn_slices(L, h->slices)), dim3(256), ATTN_LDS, st, qkv, bias, A, L, W, ascale);
+    LAUNCH_CHECK();
+    return HEDIT_OK;
+  };
+  for (const EncBlock& k : h->blocks) TRY(enc_block_forward(f, k, T, M, W, P_QGELU, LN_EPS, attn));
   // ln_post on the class row, times visual.proj: text.hip's pooled path with row 0
   float *Rw, *N, *o;
   TRY(palloc(f, &Rw, (size_t)B * W));
-  if (!dry) { hipLaunchKernelGGL(class_rows_kernel, egrid((long)B * W), dim3(256), 0, st, T, Rw, B, L, W); LAUNCH_CHECK(); }
+  if (!dry) TRY(enc_gather_rows_launch(T, nullptr, Rw, B, L, W, st));
   TRY(palloc(f, &N, (size_t)B * W));
-  TRY(ln(f, Rw, h->lnog, h->lnob, B, W, N));
-  TRY(lin(f, N, W, P_COPY, nullptr, h->proj, true, B, &o));             // one M = B GEMM: x @ visual.proj
+  TRY(ln(f, Rw, h->lnog, h->lnob, B, W, LN_EPS, N));
+  TRY(lin(f, N, W, P_COPY, nullptr, nullptr, h->proj, true, B, &o));            // one M = B GEMM: x @ visual.proj
   if (!dry) HIP_TRY(hipMemcpyAsync(out, o, (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, st));
   f.ar.free(o);
   f.ar.free(N);
@@ -333,30 +220,16 @@ int hedit_clipimg_create(const hedit_clipimg_cfg* cfg, hedit_clipimg** out) try 
   h->cfg = *cfg;
   h->P = P; h->L = L;
   const int W = cfg->width, p = cfg->patch_size, E = cfg->embed_dim;
-  auto mat = [&](const std::string& name, int O, int I) {
-    float* d = dalloc<float>(h, (size_t)O * I);
-    add_slot(h, name, 0, d, (size_t)O * I, O, I, 2, O, I, 1, 1);
-    return d;
-  };
   h->conv_w = f32conv(h, "visual.conv1.weight", W, 3, p);
   h->cls = vec(h, "visual.class_embedding", W);
-  h->pos = mat("visual.positional_embedding", L, W);
+  h->pos = mat(h, "visual.positional_embedding", L, W);
   h->lnpg = vec(h, "visual.ln_pre.weight", W);
   h->lnpb = vec(h, "visual.ln_pre.bias", W);
-  for (int i = 0; i < cfg->layers; ++i) {
-    const std::string pre = "visual.transformer.resblocks." + std::to_string(i);
-    CBlock k{};
-    k.ln1g = vec(h, pre + ".ln_1.weight", W); k.ln1b = vec(h, pre + ".ln_1.bias", W);
-    k.win = mat(pre + ".attn.in_proj_weight", 3 * W, W); k.bin = vec(h, pre + ".attn.in_proj_bias", 3 * W);
-    k.wo = mat(pre + ".attn.out_proj.weight", W, W); k.bo = vec(h, pre + ".attn.out_proj.bias", W);
-    k.ln2g = vec(h, pre + ".ln_2.weight", W); k.ln2b = vec(h, pre + ".ln_2.bias", W);
-    k.wfc = mat(pre + ".mlp.c_fc.weight", 4 * W, W); k.bfc = vec(h, pre + ".mlp.c_fc.bias", 4 * W);
-    k.wp = mat(pre + ".mlp.c_proj.weight", W, 4 * W); k.bp = vec(h, pre + ".mlp.c_proj.bias", W);
-    h->blocks.push_back(k);
-  }
+  for (int i = 0; i < cfg->layers; ++i)
+    h->blocks.push_back(enc_add_block(h, "visual.transformer.resblocks." + std::to_string(i), CLIP_BLOCK_NAMES, W));
   h->lnog = vec(h, "visual.ln_post.weight", W);
   h->lnob = vec(h, "visual.ln_post.bias", W);
-  h->proj_w = mat("visual.proj", W, E);
+  h->proj_w = mat(h, "visual.proj", W, E);
   if (h->alloc_failed) {
     hedit_set_error("hipMalloc failed while creating the CLIP image tower");
     store_free(h);
@@ -373,17 +246,9 @@ void hedit_clipimg_destroy(hedit_clipimg* h) try {
   delete h;
 } catch (...) { (void)hedit_abi_catch(); }
 
-int hedit_clipimg_num_params(const hedit_clipimg* h) { return h ? (int)h->slots.size() : 0; }
-const char* hedit_clipimg_param_name(const hedit_clipimg* h, int i) try {
-  if (!h || i < 0 || i >= (int)h->slots.size()) return nullptr;
-  return h->slots[i].name.c_str();
-} catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_clipimg_param_shape(const hedit_clipimg* h, int i, int* ndim, int* dims4) try {
-  ARG_CHECK(h && ndim && dims4 && i >= 0 && i < (int)h->slots.size(), "param index");
-  *ndim = h->slots[i].ndim;
-  for (int k = 0; k < 4; ++k) dims4[k] = h->slots[i].dims[k];
-  return HEDIT_OK;
-} catch (...) { return hedit_abi_catch(); }
+int hedit_clipimg_num_params(const hedit_clipimg* h) { return store_num_params(h); }
+const char* hedit_clipimg_param_name(const hedit_clipimg* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
+int hedit_clipimg_param_shape(const hedit_clipimg* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
 int hedit_clipimg_load(hedit_clipimg* h, const char* name, const float* w, size_t numel, void* stream) try {
   ARG_CHECK(h && name && w, "null");
   h->finalized = false;
@@ -401,12 +266,7 @@ int hedit_clipimg_finalize(hedit_clipimg* h, void* stream) try {
   const int W = h->cfg.width, p = h->cfg.patch_size;
   // conv1 weight [W][3][p][p] flattened = a linear map over (c, ky, kx)
   TRY(pack_fwd(h, h->conv, h->conv_w, W, 3 * p * p, false, st));
-  for (CBlock& k : h->blocks) {
-    TRY(pack_fwd(h, k.in, k.win, 3 * W, W, false, st));
-    TRY(pack_fwd(h, k.out, k.wo, W, W, false, st));
-    TRY(pack_fwd(h, k.fc, k.wfc, 4 * W, W, false, st));
-    TRY(pack_fwd(h, k.proj, k.wp, W, 4 * W, false, st));
-  }
+  for (EncBlock& k : h->blocks) TRY(enc_pack_block(h, k, W, true, st));
   TRY(pack_fwd(h, h->proj, h->proj_w, W, h->cfg.embed_dim, true, st));
   if (int rc = hedit_dyn_lds(reinterpret_cast<const void*>(&tiled_attn_kernel), (int)ATTN_LDS)) return rc;
   HIP_TRY(hipStreamSynchronize(st));
@@ -439,11 +299,7 @@ int hedit_clipimg_encode(hedit_clipimg* h, const float* image, int B, float* out
   if (!h->finalized) { hedit_set_error("call hedit_clipimg_finalize after loading the parameters"); return HEDIT_ERR_STATE; }
   size_t need = 0;
   TRY(run(h, nullptr, B, out, nullptr, 0, nullptr, true, &need));
-  if (workspace_bytes < need) {
-    hedit_set_error("bad argument: clipimg_encode: workspace too small (need " + std::to_string(need) + " bytes, got " +
-                    std::to_string(workspace_bytes) + ")");
-    return HEDIT_ERR_ARG;
-  }
+  TRY(ws_check("clipimg_encode", need, workspace_bytes));
   return run(h, image, B, out, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false, nullptr);
 } catch (...) { return hedit_abi_catch(); }
 

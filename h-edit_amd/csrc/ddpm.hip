@@ -564,17 +564,9 @@ void hedit_ddpm_destroy(hedit_ddpm* h) try {
   delete h;
 } catch (...) { (void)hedit_abi_catch(); }
 
-int hedit_ddpm_num_params(const hedit_ddpm* h) { return h ? (int)h->slots.size() : 0; }
-const char* hedit_ddpm_param_name(const hedit_ddpm* h, int i) try {
-  if (!h || i < 0 || i >= (int)h->slots.size()) return nullptr;
-  return h->slots[i].name.c_str();
-} catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_ddpm_param_shape(const hedit_ddpm* h, int i, int* ndim, int* dims4) try {
-  ARG_CHECK(h && ndim && dims4 && i >= 0 && i < (int)h->slots.size(), "param index");
-  *ndim = h->slots[i].ndim;
-  for (int k = 0; k < 4; ++k) dims4[k] = h->slots[i].dims[k];
-  return HEDIT_OK;
-} catch (...) { return hedit_abi_catch(); }
+int hedit_ddpm_num_params(const hedit_ddpm* h) { return store_num_params(h); }
+const char* hedit_ddpm_param_name(const hedit_ddpm* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
+int hedit_ddpm_param_shape(const hedit_ddpm* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
 int hedit_ddpm_load(hedit_ddpm* h, const char* name, const float* w, size_t numel, void* stream) try {
   ARG_CHECK(h && name && w, "null");
   return store_load(h, "DDPM UNet", name, w, numel, reinterpret_cast<hipStream_t>(stream));

@@ -13,12 +13,13 @@
 // Arithmetic as in clipimg.hip: fp32 token stream, LayerNorm / softmax / GELU in fp32, every linear layer a three-term
 // split-bf16 product with fp32 accumulation (pnet.hip), canonical chunk order with the batch in M: a batch gives the bytes
 // of single calls.  The output is fp32 and nothing here reads the storage type, so both builds give the same bits.  The
-// small kernels clipimg.hip / vit.hip / text.hip also have are restated here: none of those files is touched.
+// kernels every encoder runs (patches, tokens with the conv bias, LayerNorm with eps 1e-6, out = res + raw + bias, and the
+// same without a residual for the keys) are those of encoder.hip and the block forward is encoder.h's.
 //
-// New here: the preprocess kernel, attention for any token count on the exact-fp32 matrix instruction
+// This file's own: the preprocess kernel, attention for any token count on the exact-fp32 matrix instruction
 // (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain), and the self-similarity head, which forms both Gram tiles on
 // the same instruction and never writes an L x L matrix.
-#include "pnet.h"
+#include "encoder.h"
 
 namespace {
 
@@ -59,55 +60,6 @@ __global__ __launch_bounds__(256) void prep_kernel(const float* __restrict__ x, 
     const float m = c == 0 ? mean[0] : (c == 1 ? mean[1] : mean[2]), s = c == 0 ? sd[0] : (c == 1 ? sd[1] : sd[2]);
     y[i] = (v - m) / s;
   }
-}
-
-// img [B][3][R][R] -> X [B*P*P][3*p*p], column = (c, ky, kx): the patch conv with kernel = stride = p is a linear map
-__global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__ img, float* __restrict__ X, int B, int R, int p) {
-  const int P = R / p, K = 3 * p * p;
-  const long total = (long)B * P * P * K;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int k = (int)(i % K);
-    const long row = i / K;
-    const int b = (int)(row / (P * P)), pr = (int)(row % (P * P));
-    const int c = k / (p * p), ky = (k / p) % p, kx = k % p;
-    X[i] = img[(((long)b * 3 + c) * R + (pr / P) * p + ky) * R + (pr % P) * p + kx];
-  }
-}
-// T[b][0] = cls + pos[0]; T[b][1+l] = (E[b][l] + conv bias) + pos[1+l]
-__global__ __launch_bounds__(256) void tokens_kernel(const float* __restrict__ E, const float* __restrict__ cbias, const float* __restrict__ cls,
-                                                     const float* __restrict__ pos, float* __restrict__ T, int B, int L, int W) {
-  const long total = (long)B * L * W;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int w = (int)(i % W);
-    const long row = i / W;
-    const int b = (int)(row / L), l = (int)(row % L);
-    T[i] = (l == 0 ? cls[w] : E[((long)b * (L - 1) + l - 1) * W + w] + cbias[w]) + pos[(long)l * W + w];
-  }
-}
-// LayerNorm over W, one wave per row (the arithmetic of clipimg.hip's ln_kernel with eps 1e-6)
-__global__ __launch_bounds__(256) void ln_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b,
-                                                 float* __restrict__ y, long rows, int W) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* xr = x + row * W;
-  float s = 0.f;
-  for (int i = lane; i < W; i += 64) s += xr[i];
-  const float mean = wave_sum(s) / (float)W;
-  float q = 0.f;
-  for (int i = lane; i < W; i += 64) { const float d = xr[i] - mean; q += d * d; }
-  const float rstd = rsqrtf(wave_sum(q) / (float)W + LN_EPS);
-  for (int i = lane; i < W; i += 64) y[row * W + i] = (xr[i] - mean) * rstd * g[i] + b[i];
-}
-// out = res + raw + bias
-__global__ __launch_bounds__(256) void add_bias_res_kernel(const float* __restrict__ raw, const float* __restrict__ bias, const float* __restrict__ res,
-                                                           float* __restrict__ out, long total, int W) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) out[i] = res[i] + raw[i] + bias[i % W];
-}
-// out = raw + bias: the keys
-__global__ __launch_bounds__(256) void add_bias_kernel(const float* __restrict__ raw, const float* __restrict__ bias, float* __restrict__ out,
-                                                       long total, int W) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) out[i] = raw[i] + bias[i % W];
 }
 
 // ---- bidirectional attention over the L tokens of one image, head dimension 64, fp32, any L, on v_mfma_f32_32x32x2_f32.
@@ -308,22 +260,9 @@ __global__ __launch_bounds__(256) void selfsim_sum_kernel(const float* __restric
   if (threadIdx.x == 0) dist[n] = s[0] / ((float)L * (float)L);
 }
 
-struct DBlock {
-  float *ln1g, *ln1b, *ln2g, *ln2b, *win, *bin, *wo, *bo, *wfc, *bfc, *wp, *bp;
-  PConv in, out, fc, proj;
-};
-
-inline dim3 egrid(long total) { return dim3(ew_grid(total)); }
-
-// forward-only packed weight of out = x . w^T, w [O][I] (clipimg.hip's pack_fwd without the transposed form)
-int pack_fwd(ParamStore* h, PConv& c, const float* w, int O, int I, hipStream_t st) {
-  c.O = O; c.I = I; c.k = 1;
-  c.rows_f = (O + 3) / 4 * 4;
-  c.rows_b = (I + 3) / 4 * 4;
-  if (!c.wf) c.wf = dalloc<bf16_t>(h, (size_t)c.rows_f * split_kp(I));
-  if (!c.wf) { hedit_set_error("hipMalloc failed for a packed weight"); return HEDIT_ERR_HIP; }
-  return pack_split3_w_launch(w, nullptr, c.wf, O, I, 1, 0, split_cs(I), split_kp(I), c.rows_f, 0, 0, st);
-}
+// facebookresearch/dino vision_transformer.py: blocks.<i>
+constexpr EncNames DINO_BLOCK_NAMES = {{".norm1.weight", ".norm1.bias", ".attn.qkv.weight", ".attn.qkv.bias", ".attn.proj.weight", ".attn.proj.bias",
+                                        ".norm2.weight", ".norm2.bias", ".mlp.fc1.weight", ".mlp.fc1.bias", ".mlp.fc2.weight", ".mlp.fc2.bias"}};
 
 }  // namespace
 
@@ -333,29 +272,13 @@ struct hedit_dino : ParamStore {
   int slices = 0;                 // > 0: the attention grid's slice count (hedit_dino_set_slices), else one per pass
   float *conv_w = nullptr, *conv_b = nullptr, *cls = nullptr, *pos = nullptr;
   PConv conv;
-  std::vector<DBlock> blocks;     // key_layer whole blocks
+  std::vector<EncBlock> blocks;   // key_layer whole blocks
   float *kln_g = nullptr, *kln_b = nullptr, *kw = nullptr, *kb = nullptr;      // block key_layer: norm1 and the fused qkv (its key third is used)
   PConv key;
   bool finalized = false;
 };
 
 namespace {
-
-int ln(PF& f, const float* x, const float* g, const float* b, long rows, int W, float* y) {
-  if (!f.dry()) {
-    hipLaunchKernelGGL(ln_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, f.st, x, g, b, y, rows, W);
-    LAUNCH_CHECK();
-  }
-  return HEDIT_OK;
-}
-
-int lin(PF& f, const float* x, int C, int op, const float* q, const PConv& c, long M, float** out) {
-  bf16_t* A;
-  TRY(op_split(f, x, C, op, nullptr, q, 0, nullptr, 0, 1, 1, M, &A));
-  TRY(pgemm(f, A, c, false, 0, 1, 1, M, out));
-  f.ar.free(A);
-  return HEDIT_OK;
-}
 
 // image [B][3][S][S] (0..255, masked) -> keys [B][L][W] (workspace or caller memory; written by the last kernel)
 int run_keys(hedit_dino* h, PF& f, const float* image, int B, int S, float* keys) {
@@ -369,61 +292,29 @@ int run_keys(hedit_dino* h, PF& f, const float* image, int B, int S, float* keys
   TRY(palloc(f, &img, (size_t)B * 3 * R * R));
   if (!dry) { hipLaunchKernelGGL(prep_kernel, egrid((long)B * 3 * R * R), dim3(256), 0, st, image, img, B, S, R); LAUNCH_CHECK(); }
   TRY(palloc(f, &X0, (size_t)Mp * K0));
-  if (!dry) { hipLaunchKernelGGL(patchify_kernel, egrid(Mp * K0), dim3(256), 0, st, img, X0, B, R, p); LAUNCH_CHECK(); }
-  TRY(lin(f, X0, K0, P_COPY, nullptr, h->conv, Mp, &Em));
+  if (!dry) TRY(enc_patchify_launch(img, X0, B, R, p, 0, st));
+  TRY(lin(f, X0, K0, P_COPY, nullptr, nullptr, h->conv, false, Mp, &Em));
   TRY(palloc(f, &T, (size_t)M * W));
-  if (!dry) { hipLaunchKernelGGL(tokens_kernel, egrid(M * W), dim3(256), 0, st, Em, h->conv_b, h->cls, h->pos, T, B, L, W); LAUNCH_CHECK(); }
+  if (!dry) TRY(enc_tokens_launch(Em, h->conv_b, h->cls, h->pos, T, B, L, W, st));
   f.ar.free(Em);
   f.ar.free(X0);
   f.ar.free(img);
-  for (const DBlock& k : h->blocks) {
-    float *a, *qkv, *A, *raw, *Tmid, *m, *H, *Tn;
-    TRY(palloc(f, &a, (size_t)M * W));
-    TRY(ln(f, T, k.ln1g, k.ln1b, M, W, a));
-    TRY(lin(f, a, W, P_COPY, nullptr, k.in, M, &qkv));
-    f.ar.free(a);
-    TRY(palloc(f, &A, (size_t)M * W));
-    if (!dry) {
-      hipLaunchKernelGGL(mfma_attn_kernel, dim3(heads, B, attn_slices(L, h->slices)), dim3(256), ATTN_LDS, st, qkv, k.bin, A, L, W, ascale);
-      LAUNCH_CHECK();
-    }
-    f.ar.free(qkv);
-    TRY(lin(f, A, W, P_COPY, nullptr, k.out, M, &raw));
-    f.ar.free(A);
-    TRY(palloc(f, &Tmid, (size_t)M * W));
-    if (!dry) { hipLaunchKernelGGL(add_bias_res_kernel, egrid(M * W), dim3(256), 0, st, raw, k.bo, T, Tmid, M * W, W); LAUNCH_CHECK(); }
-    f.ar.free(raw);
-    f.ar.free(T);
-    TRY(palloc(f, &m, (size_t)M * W));
-    TRY(ln(f, Tmid, k.ln2g, k.ln2b, M, W, m));
-    TRY(lin(f, m, W, P_COPY, nullptr, k.fc, M, &H));
-    f.ar.free(m);
-    TRY(lin(f, H, 4 * W, P_GELU, k.bfc, k.proj, M, &raw));             // exact GELU(H + bias) as the operand op
-    f.ar.free(H);
-    TRY(palloc(f, &Tn, (size_t)M * W));
-    if (!dry) { hipLaunchKernelGGL(add_bias_res_kernel, egrid(M * W), dim3(256), 0, st, raw, k.bp, Tmid, Tn, M * W, W); LAUNCH_CHECK(); }
-    f.ar.free(raw);
-    f.ar.free(Tmid);
-    T = Tn;
-  }
+  auto attn = [&](const float* qkv, const float* bias, float* A) -> int {
+    hipLaunchKernelGGL(mfma_attn_kernel, dim3(heads, B, attn_slices(L, h->slices)), dim3(256), ATTN_LDS, st, qkv, bias, A, L, W, ascale);
+    LAUNCH_CHECK();
+    return HEDIT_OK;
+  };
+  for (const EncBlock& k : h->blocks) TRY(enc_block_forward(f, k, T, M, W, P_GELU, LN_EPS, attn));      // exact (erf) GELU
   // block key_layer: norm1 and the key third of qkv
   float *a, *raw;
   TRY(palloc(f, &a, (size_t)M * W));
-  TRY(ln(f, T, h->kln_g, h->kln_b, M, W, a));
-  TRY(lin(f, a, W, P_COPY, nullptr, h->key, M, &raw));
-  if (!dry) { hipLaunchKernelGGL(add_bias_kernel, egrid(M * W), dim3(256), 0, st, raw, h->kb + W, keys, M * W, W); LAUNCH_CHECK(); }
+  TRY(ln(f, T, h->kln_g, h->kln_b, M, W, LN_EPS, a));
+  TRY(lin(f, a, W, P_COPY, nullptr, nullptr, h->key, false, M, &raw));
+  if (!dry) TRY(enc_add_bias_res_launch(raw, h->kb + W, nullptr, keys, M * W, W, st));      // out = raw + bias: the keys
   f.ar.free(raw);
   f.ar.free(a);
   f.ar.free(T);
   return HEDIT_OK;
-}
-
-PF make_pf(int B, void* ws, size_t ws_bytes, hipStream_t st, bool dry) {
-  PF f{B, st, Arena{}};
-  f.ar.dry = dry;
-  f.ar.base = reinterpret_cast<char*>(ws);
-  f.ar.cap = ws_bytes;
-  return f;
 }
 
 int run_keys_entry(hedit_dino* h, const float* image, int B, int S, float* keys, void* ws, size_t ws_bytes, hipStream_t st, bool dry, size_t* peak) {
@@ -485,11 +376,6 @@ int hedit_dino_create(const hedit_dino_cfg* cfg, hedit_dino** out) try {
   h->cfg = *cfg;
   h->P = (int)P; h->L = L;
   const int W = cfg->width, p = cfg->patch_size;
-  auto mat = [&](const std::string& name, int O, int I) {
-    float* d = dalloc<float>(h, (size_t)O * I);
-    add_slot(h, name, 0, d, (size_t)O * I, O, I, 2, O, I, 1, 1);
-    return d;
-  };
   {
     h->cls = dalloc<float>(h, W);
     add_slot(h, "cls_token", 0, h->cls, W, 0, 0, 3, 1, 1, W, 1);
@@ -498,21 +384,12 @@ int hedit_dino_create(const hedit_dino_cfg* cfg, hedit_dino** out) try {
   }
   h->conv_w = f32conv(h, "patch_embed.proj.weight", W, 3, p);
   h->conv_b = vec(h, "patch_embed.proj.bias", W);
-  for (int i = 0; i < cfg->key_layer; ++i) {
-    const std::string pre = "blocks." + std::to_string(i);
-    DBlock k{};
-    k.ln1g = vec(h, pre + ".norm1.weight", W); k.ln1b = vec(h, pre + ".norm1.bias", W);
-    k.win = mat(pre + ".attn.qkv.weight", 3 * W, W); k.bin = vec(h, pre + ".attn.qkv.bias", 3 * W);
-    k.wo = mat(pre + ".attn.proj.weight", W, W); k.bo = vec(h, pre + ".attn.proj.bias", W);
-    k.ln2g = vec(h, pre + ".norm2.weight", W); k.ln2b = vec(h, pre + ".norm2.bias", W);
-    k.wfc = mat(pre + ".mlp.fc1.weight", 4 * W, W); k.bfc = vec(h, pre + ".mlp.fc1.bias", 4 * W);
-    k.wp = mat(pre + ".mlp.fc2.weight", W, 4 * W); k.bp = vec(h, pre + ".mlp.fc2.bias", W);
-    h->blocks.push_back(k);
-  }
+  for (int i = 0; i < cfg->key_layer; ++i) h->blocks.push_back(enc_add_block(h, "blocks." + std::to_string(i), DINO_BLOCK_NAMES, W));
   {
     const std::string pre = "blocks." + std::to_string(cfg->key_layer);
-    h->kln_g = vec(h, pre + ".norm1.weight", W); h->kln_b = vec(h, pre + ".norm1.bias", W);
-    h->kw = mat(pre + ".attn.qkv.weight", 3 * W, W); h->kb = vec(h, pre + ".attn.qkv.bias", 3 * W);
+    const EncNames& n = DINO_BLOCK_NAMES;
+    h->kln_g = vec(h, pre + n.s[0], W); h->kln_b = vec(h, pre + n.s[1], W);
+    h->kw = mat(h, pre + n.s[2], 3 * W, W); h->kb = vec(h, pre + n.s[3], 3 * W);
   }
   if (h->alloc_failed) {
     hedit_set_error("hipMalloc failed while creating the DINO ViT");
@@ -530,17 +407,9 @@ void hedit_dino_destroy(hedit_dino* h) try {
   delete h;
 } catch (...) { (void)hedit_abi_catch(); }
 
-int hedit_dino_num_params(const hedit_dino* h) { return h ? (int)h->slots.size() : 0; }
-const char* hedit_dino_param_name(const hedit_dino* h, int i) try {
-  if (!h || i < 0 || i >= (int)h->slots.size()) return nullptr;
-  return h->slots[i].name.c_str();
-} catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_dino_param_shape(const hedit_dino* h, int i, int* ndim, int* dims4) try {
-  ARG_CHECK(h && ndim && dims4 && i >= 0 && i < (int)h->slots.size(), "param index");
-  *ndim = h->slots[i].ndim;
-  for (int k = 0; k < 4; ++k) dims4[k] = h->slots[i].dims[k];
-  return HEDIT_OK;
-} catch (...) { return hedit_abi_catch(); }
+int hedit_dino_num_params(const hedit_dino* h) { return store_num_params(h); }
+const char* hedit_dino_param_name(const hedit_dino* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
+int hedit_dino_param_shape(const hedit_dino* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
 int hedit_dino_load(hedit_dino* h, const char* name, const float* w, size_t numel, void* stream) try {
   ARG_CHECK(h && name && w, "null");
   h->finalized = false;
@@ -556,14 +425,9 @@ int hedit_dino_finalize(hedit_dino* h, void* stream) try {
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int W = h->cfg.width, p = h->cfg.patch_size;
-  TRY(pack_fwd(h, h->conv, h->conv_w, W, 3 * p * p, st));
-  for (DBlock& k : h->blocks) {
-    TRY(pack_fwd(h, k.in, k.win, 3 * W, W, st));
-    TRY(pack_fwd(h, k.out, k.wo, W, W, st));
-    TRY(pack_fwd(h, k.fc, k.wfc, 4 * W, W, st));
-    TRY(pack_fwd(h, k.proj, k.wp, W, 4 * W, st));
-  }
-  TRY(pack_fwd(h, h->key, h->kw + (size_t)W * W, W, W, st));           // rows [W, 2W) of qkv: the keys
+  TRY(pack_fwd(h, h->conv, h->conv_w, W, 3 * p * p, false, st));
+  for (EncBlock& k : h->blocks) TRY(enc_pack_block(h, k, W, true, st));
+  TRY(pack_fwd(h, h->key, h->kw + (size_t)W * W, W, W, false, st));    // rows [W, 2W) of qkv: the keys
   if (int rc = hedit_dyn_lds(reinterpret_cast<const void*>(&mfma_attn_kernel), (int)ATTN_LDS)) return rc;
   HIP_TRY(hipStreamSynchronize(st));
   if (h->alloc_failed) { hedit_set_error("hipMalloc failed while packing the DINO ViT's weights"); return HEDIT_ERR_HIP; }
@@ -598,11 +462,7 @@ int hedit_dino_keys(hedit_dino* h, const float* image, int B, int S, float* keys
   ARG_CHECK(workspace, "dino_keys: null workspace");
   size_t need = 0;
   TRY(run_keys_entry(h, nullptr, B, S, nullptr, nullptr, 0, nullptr, true, &need));
-  if (workspace_bytes < need) {
-    hedit_set_error("bad argument: dino_keys: workspace too small (need " + std::to_string(need) + " bytes, got " + std::to_string(workspace_bytes) +
-                    ")");
-    return HEDIT_ERR_ARG;
-  }
+  TRY(ws_check("dino_keys", need, workspace_bytes));
   return run_keys_entry(h, image, B, S, keys, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false, nullptr);
 } catch (...) { return hedit_abi_catch(); }
 
@@ -617,11 +477,7 @@ int hedit_dino_structure_distance(hedit_dino* h, const float* a, const float* b,
   ARG_CHECK(workspace, "dino_structure_distance: null workspace");
   size_t need = 0;
   TRY(run_dist(h, nullptr, nullptr, N, S, nullptr, nullptr, 0, nullptr, true, &need));
-  if (workspace_bytes < need) {
-    hedit_set_error("bad argument: dino_structure_distance: workspace too small (need " + std::to_string(need) + " bytes, got " +
-                    std::to_string(workspace_bytes) + ")");
-    return HEDIT_ERR_ARG;
-  }
+  TRY(ws_check("dino_structure_distance", need, workspace_bytes));
   return run_dist(h, a, b, N, S, dist, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false, nullptr);
 } catch (...) { return hedit_abi_catch(); }
 

@@ -262,17 +262,9 @@ void hedit_irse50_destroy(hedit_irse* h) try {
   delete h;
 } catch (...) { (void)hedit_abi_catch(); }
 
-int hedit_irse50_num_params(const hedit_irse* h) { return h ? (int)h->slots.size() : 0; }
-const char* hedit_irse50_param_name(const hedit_irse* h, int i) try {
-  if (!h || i < 0 || i >= (int)h->slots.size()) return nullptr;
-  return h->slots[i].name.c_str();
-} catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_irse50_param_shape(const hedit_irse* h, int i, int* ndim, int* dims4) try {
-  ARG_CHECK(h && ndim && dims4 && i >= 0 && i < (int)h->slots.size(), "param index");
-  *ndim = h->slots[i].ndim;
-  for (int k = 0; k < 4; ++k) dims4[k] = h->slots[i].dims[k];
-  return HEDIT_OK;
-} catch (...) { return hedit_abi_catch(); }
+int hedit_irse50_num_params(const hedit_irse* h) { return store_num_params(h); }
+const char* hedit_irse50_param_name(const hedit_irse* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
+int hedit_irse50_param_shape(const hedit_irse* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
 int hedit_irse50_load(hedit_irse* h, const char* name, const float* w, size_t numel, void* stream) try {
   ARG_CHECK(h && name && w, "null");
   h->finalized = false;

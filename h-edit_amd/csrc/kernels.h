@@ -358,3 +358,15 @@ int maxpool2_bwd_launch(const float* gp, const uint8_t* idx, const float* add, f
 int lpips_head_launch(const float* z, const float* bias, const float* src, long src_img_stride, const float* w, float* fn_out, float* dpix,
                       float* dF, int B, int HW, int C, float gscale, hipStream_t st);
 int lpips_reduce_launch(const float* dpix, float* acc, int B, int HW, int first, hipStream_t st);
+
+// ---------------------------------------------------------------- encoder.hip (fp32 kernels shared by the transformer encoders)
+// img [B][3][R][R] -> X [B*(R/p)^2][3*p*p], column = (c, ky, kx); bwd = 1: the inverse permutation, X -> img (img is written)
+int enc_patchify_launch(const float* img, float* X, int B, int R, int p, int bwd, hipStream_t st);
+// T[b][0] = cls + pos[0]; T[b][1+l] = (E[b][l] + cbias) + pos[1+l]; cbias null: E[b][l] + pos[1+l].  E [B*(L-1)][W], T [B*L][W]
+int enc_tokens_launch(const float* E, const float* cbias, const float* cls, const float* pos, float* T, int B, int L, int W, hipStream_t st);
+// R[b] = T[b][clamp(idx[b])] of T [B][L][W]; idx null: row 0
+int enc_gather_rows_launch(const float* T, const int32_t* idx, float* R, int B, int L, int W, hipStream_t st);
+// LayerNorm over the W columns of [rows][W], one wave per row; stats (or null) [rows][2] = (mean, rstd)
+int enc_ln_launch(const float* x, const float* g, const float* b, float* y, float* stats, long rows, int W, float eps, hipStream_t st);
+// out = res + raw + bias[i % W]; res null: raw + bias
+int enc_add_bias_res_launch(const float* raw, const float* bias, const float* res, float* out, long total, int W, hipStream_t st);

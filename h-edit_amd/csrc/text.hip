@@ -9,9 +9,9 @@
 // of single calls.  The output is fp32 and nothing here reads the storage type, so both builds give the same bits.
 // Parameters by the OpenAI CLIP state_dict names (`token_embedding.weight`, `transformer.resblocks.0.attn.in_proj_weight` ...).
 //
-// The small kernels vit.hip also has (LayerNorm forward, out = res + raw + bias, the LDS row helpers) are restated here
-// without the backward pass's by-products (statistics, log-sum-exp) rather than shared: vit.hip is not touched.
-#include "pnet.h"
+// The kernels every encoder runs (LayerNorm, out = res + raw + bias, the row gather) are those of encoder.hip and the block
+// forward is encoder.h's; what is this file's own is the embedding gather and the causal attention kernel.
+#include "encoder.h"
 
 namespace {
 
@@ -30,37 +30,6 @@ __global__ __launch_bounds__(256) void embed_kernel(const int32_t* __restrict__ 
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
     T[i] = tok[(long)id * W + w] + pos[(long)l * W + w];
   }
-}
-// R[b] = T[b][clamp(idx[b])]
-__global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ T, const int32_t* __restrict__ idx, float* __restrict__ R,
-                                                          int B, int L, int W) {
-  const long total = (long)B * W;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int w = (int)(i % W), b = (int)(i / W);
-    int l = idx[b];
-    l = l < 0 ? 0 : (l >= L ? L - 1 : l);
-    R[i] = T[((long)b * L + l) * W + w];
-  }
-}
-// LayerNorm over W, one wave per row (the arithmetic of vit.hip's ln_fwd_kernel; no statistics are kept)
-__global__ __launch_bounds__(256) void ln_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b,
-                                                 float* __restrict__ y, long rows, int W) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* xr = x + row * W;
-  float s = 0.f;
-  for (int i = lane; i < W; i += 64) s += xr[i];
-  const float mean = wave_sum(s) / (float)W;
-  float q = 0.f;
-  for (int i = lane; i < W; i += 64) { const float d = xr[i] - mean; q += d * d; }
-  const float rstd = rsqrtf(wave_sum(q) / (float)W + LN_EPS);
-  for (int i = lane; i < W; i += 64) y[row * W + i] = (xr[i] - mean) * rstd * g[i] + b[i];
-}
-// out = res + raw + bias
-__global__ __launch_bounds__(256) void add_bias_res_kernel(const float* __restrict__ raw, const float* __restrict__ bias, const float* __restrict__ res,
-                                                           float* __restrict__ out, long total, int W) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) out[i] = res[i] + raw[i] + bias[i % W];
 }
 
 // ---- causal attention over the L tokens of one prompt, head dimension 64, fp32.  qkv: [B*L][3W] raw (bias added on load),
@@ -151,107 +120,43 @@ __global__ __launch_bounds__(256) void causal_attn_kernel(const float* __restric
   }
 }
 
-struct TBlock {
-  float *ln1g, *ln1b, *ln2g, *ln2b, *win, *bin, *wo, *bo, *wfc, *bfc, *wp, *bp;
-  PConv in, out, fc, proj;
-};
-
-inline dim3 egrid(long total) { return dim3(ew_grid(total)); }
-
-// forward-only packed weight of out = x . w^T, w [O][I] (make_pconv of pnet.h also builds the input-gradient twin, which
-// nothing here would read: 0.5 GB at SD size).  transposed: w is [O][I] and the product is x [M][O] . w -> [M][I].
-int pack_fwd(ParamStore* h, PConv& c, const float* w, int O, int I, bool transposed, hipStream_t st) {
-  c.O = O; c.I = I; c.k = 1;
-  c.rows_f = (O + 3) / 4 * 4;
-  c.rows_b = (I + 3) / 4 * 4;
-  bf16_t*& dst = transposed ? c.wb : c.wf;
-  const int rows = transposed ? c.rows_b : c.rows_f, Cin = transposed ? O : I;
-  if (!dst) dst = dalloc<bf16_t>(h, (size_t)rows * split_kp(Cin));
-  if (!dst) { hedit_set_error("hipMalloc failed for a packed weight"); return HEDIT_ERR_HIP; }
-  return pack_split3_w_launch(w, nullptr, dst, O, I, 1, transposed ? 1 : 0, split_cs(Cin), split_kp(Cin), rows, 0, 0, st);
-}
-
 }  // namespace
 
 struct hedit_text : ParamStore {
   hedit_text_cfg cfg;
   float *tok = nullptr, *pos = nullptr, *lnfg = nullptr, *lnfb = nullptr, *proj_w = nullptr;
   PConv proj;
-  std::vector<TBlock> blocks;
+  std::vector<EncBlock> blocks;
   bool finalized = false;
 };
 
 namespace {
 
-int ln(PF& f, const float* x, const float* g, const float* b, long rows, int W, float* y) {
-  if (!f.dry()) {
-    hipLaunchKernelGGL(ln_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, f.st, x, g, b, y, rows, W);
-    LAUNCH_CHECK();
-  }
-  return HEDIT_OK;
-}
-
-// the M rows of a [M][C] fp32 tensor as a split operand and through one linear layer: out raw [M][N]
-int lin(PF& f, const float* x, int C, int op, const float* q, const PConv& c, bool transposed, long M, float** out) {
-  bf16_t* A;
-  TRY(op_split(f, x, C, op, nullptr, q, 0, nullptr, 0, 1, 1, M, &A));
-  TRY(pgemm(f, A, c, transposed, 0, 1, 1, M, out));
-  f.ar.free(A);
-  return HEDIT_OK;
-}
-
 int run(hedit_text* h, const int32_t* ids, int B, int L, float* hidden, const int32_t* pool_index, float* pooled, void* ws, size_t ws_bytes,
         hipStream_t st, bool dry, size_t* peak) {
-  PF f{B, st, Arena{}};
-  f.ar.dry = dry;
-  f.ar.base = reinterpret_cast<char*>(ws);
-  f.ar.cap = ws_bytes;
+  PF f = make_pf(B, ws, ws_bytes, st, dry);
   const int W = h->cfg.width, heads = h->cfg.heads, P = h->cfg.proj_dim;
   const long M = (long)B * L;
   const float ascale = 1.0f / sqrtf((float)HD);
   float* T;
   TRY(palloc(f, &T, (size_t)M * W));
   if (!dry) { hipLaunchKernelGGL(embed_kernel, egrid(M * W), dim3(256), 0, st, ids, h->tok, h->pos, T, M, L, W, h->cfg.vocab_size); LAUNCH_CHECK(); }
-  for (const TBlock& k : h->blocks) {
-    float *a, *qkv, *A, *raw, *Tmid, *m, *H, *Tn;
-    TRY(palloc(f, &a, (size_t)M * W));
-    TRY(ln(f, T, k.ln1g, k.ln1b, M, W, a));
-    TRY(lin(f, a, W, P_COPY, nullptr, k.in, false, M, &qkv));
-    f.ar.free(a);
-    TRY(palloc(f, &A, (size_t)M * W));
-    if (!dry) {
-      hipLaunchKernelGGL(causal_attn_kernel, dim3(heads, B, attn_slices(heads, B)), dim3(256), attn_lds(L), st, qkv, k.bin, A, L, W, ascale);
-      LAUNCH_CHECK();
-    }
-    f.ar.free(qkv);
-    TRY(lin(f, A, W, P_COPY, nullptr, k.out, false, M, &raw));
-    f.ar.free(A);
-    TRY(palloc(f, &Tmid, (size_t)M * W));
-    if (!dry) { hipLaunchKernelGGL(add_bias_res_kernel, egrid(M * W), dim3(256), 0, st, raw, k.bo, T, Tmid, M * W, W); LAUNCH_CHECK(); }
-    f.ar.free(raw);
-    f.ar.free(T);
-    TRY(palloc(f, &m, (size_t)M * W));
-    TRY(ln(f, Tmid, k.ln2g, k.ln2b, M, W, m));
-    TRY(lin(f, m, W, P_COPY, nullptr, k.fc, false, M, &H));
-    f.ar.free(m);
-    TRY(lin(f, H, 4 * W, P_QGELU, k.bfc, k.proj, false, M, &raw));      // QuickGELU(H + bias) as the operand op
-    f.ar.free(H);
-    TRY(palloc(f, &Tn, (size_t)M * W));
-    if (!dry) { hipLaunchKernelGGL(add_bias_res_kernel, egrid(M * W), dim3(256), 0, st, raw, k.bp, Tmid, Tn, M * W, W); LAUNCH_CHECK(); }
-    f.ar.free(raw);
-    f.ar.free(Tmid);
-    T = Tn;
-  }
-  if (hidden) TRY(ln(f, T, h->lnfg, h->lnfb, M, W, hidden));
+  auto attn = [&](const float* qkv, const float* bias, float* A) -> int {
+    hipLaunchKernelGGL(causal_attn_kernel, dim3(heads, B, attn_slices(heads, B)), dim3(256), attn_lds(L), st, qkv, bias, A, L, W, ascale);
+    LAUNCH_CHECK();
+    return HEDIT_OK;
+  };
+  for (const EncBlock& k : h->blocks) TRY(enc_block_forward(f, k, T, M, W, P_QGELU, LN_EPS, attn));
+  if (hidden) TRY(ln(f, T, h->lnfg, h->lnfb, M, W, LN_EPS, hidden));
   if (pooled) {
     // the ln_final row at pool_index[b]: gathered before the LayerNorm (a per-row operation, so the bits are those of `hidden`)
     float *R, *N = nullptr, *out;
     TRY(palloc(f, &R, (size_t)B * W));
-    if (!dry) { hipLaunchKernelGGL(gather_rows_kernel, egrid((long)B * W), dim3(256), 0, st, T, pool_index, R, B, L, W); LAUNCH_CHECK(); }
+    if (!dry) TRY(enc_gather_rows_launch(T, pool_index, R, B, L, W, st));
     if (P > 0) TRY(palloc(f, &N, (size_t)B * W));
-    TRY(ln(f, R, h->lnfg, h->lnfb, B, W, P > 0 ? N : pooled));
+    TRY(ln(f, R, h->lnfg, h->lnfb, B, W, LN_EPS, P > 0 ? N : pooled));
     if (P > 0) {
-      TRY(lin(f, N, W, P_COPY, nullptr, h->proj, true, B, &out));      // one M = B GEMM: x @ text_projection
+      TRY(lin(f, N, W, P_COPY, nullptr, nullptr, h->proj, true, B, &out));      // one M = B GEMM: x @ text_projection
       if (!dry) HIP_TRY(hipMemcpyAsync(pooled, out, (size_t)B * P * sizeof(float), hipMemcpyDeviceToDevice, st));
       f.ar.free(out);
       f.ar.free(N);
@@ -278,27 +183,13 @@ int hedit_text_create(const hedit_text_cfg* cfg, hedit_text** out) try {
   hedit_text* h = new hedit_text();
   h->cfg = *cfg;
   const int W = cfg->width;
-  auto mat = [&](const std::string& name, int O, int I) {
-    float* d = dalloc<float>(h, (size_t)O * I);
-    add_slot(h, name, 0, d, (size_t)O * I, O, I, 2, O, I, 1, 1);
-    return d;
-  };
-  h->tok = mat("token_embedding.weight", cfg->vocab_size, W);       // stays fp32: it is only gathered
-  h->pos = mat("positional_embedding", cfg->context_length, W);
-  for (int i = 0; i < cfg->layers; ++i) {
-    const std::string pre = "transformer.resblocks." + std::to_string(i);
-    TBlock k{};
-    k.ln1g = vec(h, pre + ".ln_1.weight", W); k.ln1b = vec(h, pre + ".ln_1.bias", W);
-    k.win = mat(pre + ".attn.in_proj_weight", 3 * W, W); k.bin = vec(h, pre + ".attn.in_proj_bias", 3 * W);
-    k.wo = mat(pre + ".attn.out_proj.weight", W, W); k.bo = vec(h, pre + ".attn.out_proj.bias", W);
-    k.ln2g = vec(h, pre + ".ln_2.weight", W); k.ln2b = vec(h, pre + ".ln_2.bias", W);
-    k.wfc = mat(pre + ".mlp.c_fc.weight", 4 * W, W); k.bfc = vec(h, pre + ".mlp.c_fc.bias", 4 * W);
-    k.wp = mat(pre + ".mlp.c_proj.weight", W, 4 * W); k.bp = vec(h, pre + ".mlp.c_proj.bias", W);
-    h->blocks.push_back(k);
-  }
+  h->tok = mat(h, "token_embedding.weight", cfg->vocab_size, W);       // stays fp32: it is only gathered
+  h->pos = mat(h, "positional_embedding", cfg->context_length, W);
+  for (int i = 0; i < cfg->layers; ++i)
+    h->blocks.push_back(enc_add_block(h, "transformer.resblocks." + std::to_string(i), CLIP_BLOCK_NAMES, W));
   h->lnfg = vec(h, "ln_final.weight", W);
   h->lnfb = vec(h, "ln_final.bias", W);
-  if (cfg->proj_dim > 0) h->proj_w = mat("text_projection", W, cfg->proj_dim);
+  if (cfg->proj_dim > 0) h->proj_w = mat(h, "text_projection", W, cfg->proj_dim);
   if (h->alloc_failed) {
     hedit_set_error("hipMalloc failed while creating the text encoder");
     store_free(h);
@@ -315,17 +206,9 @@ void hedit_text_destroy(hedit_text* h) try {
   delete h;
 } catch (...) { (void)hedit_abi_catch(); }
 
-int hedit_text_num_params(const hedit_text* h) { return h ? (int)h->slots.size() : 0; }
-const char* hedit_text_param_name(const hedit_text* h, int i) try {
-  if (!h || i < 0 || i >= (int)h->slots.size()) return nullptr;
-  return h->slots[i].name.c_str();
-} catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_text_param_shape(const hedit_text* h, int i, int* ndim, int* dims4) try {
-  ARG_CHECK(h && ndim && dims4 && i >= 0 && i < (int)h->slots.size(), "param index");
-  *ndim = h->slots[i].ndim;
-  for (int k = 0; k < 4; ++k) dims4[k] = h->slots[i].dims[k];
-  return HEDIT_OK;
-} catch (...) { return hedit_abi_catch(); }
+int hedit_text_num_params(const hedit_text* h) { return store_num_params(h); }
+const char* hedit_text_param_name(const hedit_text* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
+int hedit_text_param_shape(const hedit_text* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
 int hedit_text_load(hedit_text* h, const char* name, const float* w, size_t numel, void* stream) try {
   ARG_CHECK(h && name && w, "null");
   h->finalized = false;
@@ -341,12 +224,7 @@ int hedit_text_finalize(hedit_text* h, void* stream) try {
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int W = h->cfg.width;
-  for (TBlock& k : h->blocks) {
-    TRY(pack_fwd(h, k.in, k.win, 3 * W, W, false, st));
-    TRY(pack_fwd(h, k.out, k.wo, W, W, false, st));
-    TRY(pack_fwd(h, k.fc, k.wfc, 4 * W, W, false, st));
-    TRY(pack_fwd(h, k.proj, k.wp, W, 4 * W, false, st));
-  }
+  for (EncBlock& k : h->blocks) TRY(enc_pack_block(h, k, W, true, st));
   if (h->cfg.proj_dim > 0) TRY(pack_fwd(h, h->proj, h->proj_w, W, h->cfg.proj_dim, true, st));
   // the limit is remembered per (kernel, device), so it is set for the longest context any handle may have
   if (int rc = hedit_dyn_lds(reinterpret_cast<const void*>(&causal_attn_kernel), (int)attn_lds(LMAX))) return rc;
@@ -378,11 +256,7 @@ int hedit_text_encode(hedit_text* h, const int32_t* ids, int B, int L, float* hi
   if (!h->finalized) { hedit_set_error("call hedit_text_finalize after loading the parameters"); return HEDIT_ERR_STATE; }
   size_t need = 0;
   TRY(run(h, nullptr, B, L, hidden, pool_index, pooled, nullptr, 0, nullptr, true, &need));
-  if (workspace_bytes < need) {
-    hedit_set_error("bad argument: text_encode: workspace too small (need " + std::to_string(need) + " bytes, got " +
-                    std::to_string(workspace_bytes) + ")");
-    return HEDIT_ERR_ARG;
-  }
+  TRY(ws_check("text_encode", need, workspace_bytes));
   return run(h, ids, B, L, hidden, pool_index, pooled, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false, nullptr);
 } catch (...) { return hedit_abi_catch(); }
 

@@ -11,37 +11,17 @@
 // product with fp32 accumulation (pnet.hip) -- finer than the reference's fp16 CLIP (model.py:414-435).  Attention
 // over the 197 tokens of an image runs in LDS-resident fp32 kernels (one workgroup per image and head).
 // Parameters by the OpenAI CLIP state_dict names (`visual.conv1.weight`, `visual.transformer.resblocks.0.attn.in_proj_weight` ...).
-#include "pnet.h"
+//
+// Patches, tokens, the LayerNorm forward (here with its statistics kept) and out = res + raw + bias are the kernels of
+// encoder.hip; the block struct, its registration and packing and the linear layer are encoder.h's.  The forward keeps a tape
+// for the backward pass, so the block loop is this file's own, as are the attention kernels (forward with log-sum-exp, dq,
+// dk / dv), the LayerNorm backward and the Gram head.
+#include "encoder.h"
 
 namespace {
 
 constexpr float LN_EPS = 1e-5f;
 
-// ---- patches.  img [B][3][R][R] -> X [B*P*P][3*p*p], column = (c, ky, kx): conv1 with kernel = stride = p is a linear map
-__global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__ img, float* __restrict__ X, int B, int R, int p, int bwd) {
-  const int P = R / p, K = 3 * p * p;
-  const long total = (long)B * P * P * K;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int k = (int)(i % K);
-    const long row = i / K;
-    const int b = (int)(row / (P * P)), pr = (int)(row % (P * P));
-    const int c = k / (p * p), ky = (k / p) % p, kx = k % p;
-    const long src = (((long)b * 3 + c) * R + (pr / P) * p + ky) * R + (pr % P) * p + kx;
-    if (bwd) const_cast<float*>(img)[src] = X[i];      // the inverse permutation (every pixel belongs to exactly one patch)
-    else X[i] = img[src];
-  }
-}
-// T0[b][0] = cls + pos[0]; T0[b][1+l] = E[b][l] + pos[1+l]
-__global__ __launch_bounds__(256) void tokens_kernel(const float* __restrict__ E, const float* __restrict__ cls, const float* __restrict__ pos,
-                                                     float* __restrict__ T, int B, int L, int W) {
-  const long total = (long)B * L * W;
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) {
-    const int w = (int)(i % W);
-    const long row = i / W;
-    const int b = (int)(row / L), l = (int)(row % L);
-    T[i] = (l == 0 ? cls[w] : E[((long)b * (L - 1) + l - 1) * W + w]) + pos[(long)l * W + w];
-  }
-}
 // dE[b][l] = dT[b][1+l]
 __global__ __launch_bounds__(256) void drop_cls_kernel(const float* __restrict__ dT, float* __restrict__ dE, int B, int L, int W) {
   const long total = (long)B * (L - 1) * W;
@@ -53,22 +33,7 @@ __global__ __launch_bounds__(256) void drop_cls_kernel(const float* __restrict__
   }
 }
 
-// ---- LayerNorm over W (one wave per row), statistics kept for the backward pass
-__global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b,
-                                                     float* __restrict__ y, float* __restrict__ stats, long rows, int W) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  const float* xr = x + row * W;
-  float s = 0.f;
-  for (int i = lane; i < W; i += 64) s += xr[i];
-  const float mean = wave_sum(s) / (float)W;
-  float q = 0.f;
-  for (int i = lane; i < W; i += 64) { const float d = xr[i] - mean; q += d * d; }
-  const float rstd = rsqrtf(wave_sum(q) / (float)W + LN_EPS);
-  for (int i = lane; i < W; i += 64) y[row * W + i] = (xr[i] - mean) * rstd * g[i] + b[i];
-  if (lane == 0) { stats[row * 2] = mean; stats[row * 2 + 1] = rstd; }
-}
+// ---- LayerNorm backward over W (one wave per row) from the statistics the forward kept:
 // dx = add + rstd * (dy g - mean(dy g) - xhat mean(dy g xhat))
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ g,
                                                      const float* __restrict__ stats, const float* __restrict__ add, float* __restrict__ dx,
@@ -92,11 +57,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
     const float v = rstd * (dr[i] * g[i] - a - xh * c);
     dx[row * W + i] = (add ? add[row * W + i] : 0.f) + v;
   }
-}
-// out = res + raw + bias
-__global__ __launch_bounds__(256) void add_bias_res_kernel(const float* __restrict__ raw, const float* __restrict__ bias, const float* __restrict__ res,
-                                                           float* __restrict__ out, long total, int W) {
-  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long)gridDim.x * 256) out[i] = res[i] + raw[i] + bias[i % W];
 }
 
 // ---- attention over the L tokens of one image, head dimension 64, fp32, K / V (or Q / dA) of one (image, head) resident in
@@ -349,12 +309,6 @@ __global__ __launch_bounds__(256) void gram_bwd_kernel(const float* __restrict__
   }
 }
 
-struct VBlock {
-  float *ln1g, *ln1b, *ln2g, *ln2b, *win, *bin, *wo, *bo, *wfc, *bfc, *wp, *bp;
-  PConv in, out, fc, proj;
-};
-
-inline dim3 egrid(long total) { return dim3(ew_grid(total)); }
 constexpr size_t ATTN_LDS_FWD = (size_t)(2 * LMAX * HP + 8 * LMAX) * 4;
 constexpr size_t ATTN_LDS_DQ = ATTN_LDS_FWD;
 constexpr size_t ATTN_LDS_DKV = (size_t)(2 * LMAX * HP + 16 * LMAX + 2 * LMAX) * 4;
@@ -372,7 +326,7 @@ struct hedit_vit : ParamStore {
   int L = 0, P = 0;
   float *conv_w = nullptr, *cls = nullptr, *pos = nullptr, *lnpg = nullptr, *lnpb = nullptr;
   PConv conv;
-  std::vector<VBlock> blocks;
+  std::vector<EncBlock> blocks;
   bool finalized = false;
 };
 
@@ -383,29 +337,13 @@ struct BTape { float *Tin, *st1, *qkv, *A, *lse, *Tmid, *st2, *H; };
 int ln_fwd(PF& f, const float* x, const float* g, const float* b, long rows, int W, float** y, float** stats) {
   TRY(palloc(f, y, (size_t)rows * W));
   TRY(palloc(f, stats, (size_t)rows * 2));
-  if (!f.dry()) {
-    hipLaunchKernelGGL(ln_fwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, f.st, x, g, b, *y, *stats, rows, W);
-    LAUNCH_CHECK();
-  }
-  return HEDIT_OK;
-}
-
-// the M rows of a [M][C] fp32 tensor as a split operand and through one linear layer: out raw [M][N]
-int lin(PF& f, const float* x, int C, int op, const float* q, const float* z, const PConv& c, bool dgrad, long M, float** out) {
-  bf16_t* A;
-  TRY(op_split(f, x, C, op, nullptr, q, 0, z, 0, 1, 1, M, &A));
-  TRY(pgemm(f, A, c, dgrad, 0, 1, 1, M, out));
-  f.ar.free(A);
-  return HEDIT_OK;
+  return ln(f, x, g, b, rows, W, LN_EPS, *y, *stats);
 }
 
 // img [B][3][R][R] (CLIP-normalised).  gram_out: write the Gram matrices [B][W][W]; else gref -> loss [B], d_img
 int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int B, float scale, float* gram_out, float* loss, float* d_img,
         void* ws, size_t ws_bytes, hipStream_t st, bool dry, bool want_grad, size_t* peak) {
-  PF f{B, st, Arena{}};
-  f.ar.dry = dry;
-  f.ar.base = reinterpret_cast<char*>(ws);
-  f.ar.cap = ws_bytes;
+  PF f = make_pf(B, ws, ws_bytes, st, dry);
   const int W = h->cfg.width, L = h->L, R = h->cfg.input_resolution, p = h->cfg.patch_size, heads = h->cfg.heads;
   const int K0 = 3 * p * p;
   const long Mp = (long)B * (L - 1), M = (long)B * L;
@@ -413,17 +351,17 @@ int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int
   const bool grad = want_grad;
   float *X0, *E, *T0, *T, *stp;
   TRY(palloc(f, &X0, (size_t)Mp * K0));
-  if (!dry) { hipLaunchKernelGGL(patchify_kernel, egrid(Mp * K0), dim3(256), 0, st, img, X0, B, R, p, 0); LAUNCH_CHECK(); }
+  if (!dry) TRY(enc_patchify_launch(img, X0, B, R, p, 0, st));
   TRY(lin(f, X0, K0, P_COPY, nullptr, nullptr, h->conv, false, Mp, &E));
   f.ar.free(X0);
   TRY(palloc(f, &T0, (size_t)M * W));
-  if (!dry) { hipLaunchKernelGGL(tokens_kernel, egrid(M * W), dim3(256), 0, st, E, h->cls, h->pos, T0, B, L, W); LAUNCH_CHECK(); }
+  if (!dry) TRY(enc_tokens_launch(E, nullptr, h->cls, h->pos, T0, B, L, W, st));
   f.ar.free(E);
   TRY(ln_fwd(f, T0, h->lnpg, h->lnpb, M, W, &T, &stp));
   if (!grad) { f.ar.free(T0); f.ar.free(stp); }
   std::vector<BTape> tape(h->blocks.size());
   for (size_t i = 0; i < h->blocks.size(); ++i) {
-    const VBlock& k = h->blocks[i];
+    const EncBlock& k = h->blocks[i];
     BTape& t = tape[i];
     float *a, *raw, *m;
     t.Tin = T;
@@ -438,7 +376,7 @@ int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int
     }
     TRY(lin(f, t.A, W, P_COPY, nullptr, nullptr, k.out, false, M, &raw));
     TRY(palloc(f, &t.Tmid, (size_t)M * W));
-    if (!dry) { hipLaunchKernelGGL(add_bias_res_kernel, egrid(M * W), dim3(256), 0, st, raw, k.bo, t.Tin, t.Tmid, M * W, W); LAUNCH_CHECK(); }
+    if (!dry) TRY(enc_add_bias_res_launch(raw, k.bo, t.Tin, t.Tmid, M * W, W, st));
     f.ar.free(raw);
     TRY(ln_fwd(f, t.Tmid, k.ln2g, k.ln2b, M, W, &m, &t.st2));
     TRY(lin(f, m, W, P_COPY, nullptr, nullptr, k.fc, false, M, &t.H));
@@ -446,7 +384,7 @@ int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int
     TRY(lin(f, t.H, 4 * W, P_QGELU, k.bfc, nullptr, k.proj, false, M, &raw));
     float* Tn;
     TRY(palloc(f, &Tn, (size_t)M * W));
-    if (!dry) { hipLaunchKernelGGL(add_bias_res_kernel, egrid(M * W), dim3(256), 0, st, raw, k.bp, t.Tmid, Tn, M * W, W); LAUNCH_CHECK(); }
+    if (!dry) TRY(enc_add_bias_res_launch(raw, k.bp, t.Tmid, Tn, M * W, W, st));
     f.ar.free(raw);
     if (!grad) {
       f.ar.free(t.Tin); f.ar.free(t.st1); f.ar.free(t.qkv); f.ar.free(t.A); f.ar.free(t.lse); f.ar.free(t.Tmid); f.ar.free(t.st2); f.ar.free(t.H);
@@ -524,7 +462,7 @@ int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int
   f.ar.free(gpart);
   // ---- backward through the blocks
   for (int i = (int)h->blocks.size() - 1; i >= 0; --i) {
-    const VBlock& k = h->blocks[i];
+    const EncBlock& k = h->blocks[i];
     BTape& t = tape[i];
     float *dG, *dm, *dTm, *dAo, *dqkv, *da, *dTi;
     TRY(lin(f, dT, W, P_COPY, nullptr, nullptr, k.proj, true, M, &dG));                          // d QuickGELU output
@@ -560,7 +498,7 @@ int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int
   f.ar.free(dT0);
   TRY(lin(f, dE, W, P_COPY, nullptr, nullptr, h->conv, true, Mp, &dX0));
   f.ar.free(dE);
-  if (!dry) { hipLaunchKernelGGL(patchify_kernel, egrid(Mp * K0), dim3(256), 0, st, d_img, dX0, B, R, p, 1); LAUNCH_CHECK(); }
+  if (!dry) TRY(enc_patchify_launch(d_img, dX0, B, R, p, 1, st));      // the inverse permutation: dX0 -> d_img
   f.ar.free(dX0);
   if (peak) *peak = f.ar.peak;
   return HEDIT_OK;
@@ -584,26 +522,11 @@ int hedit_vit_create(const hedit_vit_cfg* cfg, hedit_vit** out) try {
   const int W = cfg->width, p = cfg->patch_size;
   h->conv_w = f32conv(h, "visual.conv1.weight", W, 3, p);
   h->cls = vec(h, "visual.class_embedding", W);
-  h->pos = dalloc<float>(h, (size_t)L * W);
-  add_slot(h, "visual.positional_embedding", 0, h->pos, (size_t)L * W, L, W, 2, L, W, 1, 1);
+  h->pos = mat(h, "visual.positional_embedding", L, W);
   h->lnpg = vec(h, "visual.ln_pre.weight", W);
   h->lnpb = vec(h, "visual.ln_pre.bias", W);
-  auto mat = [&](const std::string& name, int O, int I) {
-    float* d = dalloc<float>(h, (size_t)O * I);
-    add_slot(h, name, 0, d, (size_t)O * I, O, I, 2, O, I, 1, 1);
-    return d;
-  };
-  for (int i = 0; i < cfg->layers; ++i) {
-    const std::string pre = "visual.transformer.resblocks." + std::to_string(i);
-    VBlock k{};
-    k.ln1g = vec(h, pre + ".ln_1.weight", W); k.ln1b = vec(h, pre + ".ln_1.bias", W);
-    k.win = mat(pre + ".attn.in_proj_weight", 3 * W, W); k.bin = vec(h, pre + ".attn.in_proj_bias", 3 * W);
-    k.wo = mat(pre + ".attn.out_proj.weight", W, W); k.bo = vec(h, pre + ".attn.out_proj.bias", W);
-    k.ln2g = vec(h, pre + ".ln_2.weight", W); k.ln2b = vec(h, pre + ".ln_2.bias", W);
-    k.wfc = mat(pre + ".mlp.c_fc.weight", 4 * W, W); k.bfc = vec(h, pre + ".mlp.c_fc.bias", 4 * W);
-    k.wp = mat(pre + ".mlp.c_proj.weight", W, 4 * W); k.bp = vec(h, pre + ".mlp.c_proj.bias", W);
-    h->blocks.push_back(k);
-  }
+  for (int i = 0; i < cfg->layers; ++i)
+    h->blocks.push_back(enc_add_block(h, "visual.transformer.resblocks." + std::to_string(i), CLIP_BLOCK_NAMES, W));
   if (h->alloc_failed) {
     hedit_set_error("hipMalloc failed while creating the ViT prefix");
     store_free(h);
@@ -620,17 +543,9 @@ void hedit_vit_destroy(hedit_vit* h) try {
   delete h;
 } catch (...) { (void)hedit_abi_catch(); }
 
-int hedit_vit_num_params(const hedit_vit* h) { return h ? (int)h->slots.size() : 0; }
-const char* hedit_vit_param_name(const hedit_vit* h, int i) try {
-  if (!h || i < 0 || i >= (int)h->slots.size()) return nullptr;
-  return h->slots[i].name.c_str();
-} catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_vit_param_shape(const hedit_vit* h, int i, int* ndim, int* dims4) try {
-  ARG_CHECK(h && ndim && dims4 && i >= 0 && i < (int)h->slots.size(), "param index");
-  *ndim = h->slots[i].ndim;
-  for (int k = 0; k < 4; ++k) dims4[k] = h->slots[i].dims[k];
-  return HEDIT_OK;
-} catch (...) { return hedit_abi_catch(); }
+int hedit_vit_num_params(const hedit_vit* h) { return store_num_params(h); }
+const char* hedit_vit_param_name(const hedit_vit* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
+int hedit_vit_param_shape(const hedit_vit* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
 int hedit_vit_load(hedit_vit* h, const char* name, const float* w, size_t numel, void* stream) try {
   ARG_CHECK(h && name && w, "null");
   h->finalized = false;
@@ -648,12 +563,7 @@ int hedit_vit_finalize(hedit_vit* h, void* stream) try {
   const int W = h->cfg.width, p = h->cfg.patch_size;
   // conv1 weight [W][3][p][p] flattened = a linear map over (c, ky, kx): k = 1 with I = 3 p^2
   TRY(make_pconv(h, h->conv, h->conv_w, nullptr, W, 3 * p * p, 1, 0, 0, st));
-  for (VBlock& k : h->blocks) {
-    TRY(make_pconv(h, k.in, k.win, nullptr, 3 * W, W, 1, 0, 0, st));
-    TRY(make_pconv(h, k.out, k.wo, nullptr, W, W, 1, 0, 0, st));
-    TRY(make_pconv(h, k.fc, k.wfc, nullptr, 4 * W, W, 1, 0, 0, st));
-    TRY(make_pconv(h, k.proj, k.wp, nullptr, W, 4 * W, 1, 0, 0, st));
-  }
+  for (EncBlock& k : h->blocks) TRY(enc_pack_block(h, k, W, false, st));
   if (int rc = hedit_dyn_lds(reinterpret_cast<const void*>(&attn_fwd_kernel), (int)ATTN_LDS_FWD)) return rc;
   if (int rc = hedit_dyn_lds(reinterpret_cast<const void*>(&attn_bwd_dq_kernel), (int)ATTN_LDS_DQ)) return rc;
   if (int rc = hedit_dyn_lds(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel), (int)ATTN_LDS_DKV)) return rc;

@@ -1,4 +1,4 @@
-"""Test infrastructure for the native CLIP image tower (csrc/clipimg.hip, hedit.clip_score): hash-seeded weights under the
+"""Test infrastructure for the native CLIP image tower (csrc/clipimg.hip on csrc/encoder.hip / encoder.h, hedit.clip_score): hash-seeded weights under the
 OpenAI CLIP names (what tests/golden/make_golden_clipimg.py loaded into the reference's CLIP and into transformers'
 CLIPModel, regenerated identically by the tests -- on the device for the ViT-L/14 shape), the name mapping to
 transformers' layout, and a plain restatement of the tower in torch.  Nothing here is product code."""

@@ -1,6 +1,6 @@
 """The Structure Distance restated in torch on the CPU (fp64 by default), written from the public DINO ViT architecture
 (facebookresearch/dino vision_transformer.py) and the five steps of hedit/dino_score.py's docstring -- the reference the
-native executor (csrc/dino.hip) is tested against.  Every wrong variant the tests must be able to see is a switch here:
+native executor (csrc/dino.hip on csrc/encoder.hip / encoder.h) is tested against.  Every wrong variant the tests must be able to see is a switch here:
 ``gelu`` (erf / tanh / quick), ``eps``, ``div255``, ``antialias``, ``key_layer``, ``clamp``.
 """
 import math

@@ -1,4 +1,4 @@
-"""Test infrastructure for the native prompt encoder (csrc/text.hip, hedit.text.NativeClipText): hash-seeded weights
+"""Test infrastructure for the native prompt encoder (csrc/text.hip on csrc/encoder.hip / encoder.h, hedit.text.NativeClipText): hash-seeded weights
 under the OpenAI CLIP names (what tests/golden/make_golden_text.py loaded into the reference's CLIP and into transformers'
 CLIPTextModel, regenerated identically by the tests), the name mapping to transformers' layout, and a plain restatement
 of the text transformer in torch.  Nothing here is product code."""

@@ -1,4 +1,5 @@
-"""-m gpu: the native style encoder (hedit_vit_gram / hedit_vit_gram_fwd_bwd, csrc/vit.hip -- SURVEY.md section 8 row
+"""-m gpu: the native style encoder (hedit_vit_gram / hedit_vit_gram_fwd_bwd, csrc/vit.hip on the shared encoder kernels of
+csrc/encoder.hip -- SURVEY.md section 8 row
 a19) against (1) vectors produced by RUNNING the reference's CLIPEncoder.get_gram_matrix_residual and CLIP ViT
 (text-guided-n-style/clip_guidance/base_clip.py, clip/model.py) at toy width, tests/golden/g10_clip.npz, and (2) the
 oracle's fp32 restatement (oracle/reward_nets.py, pinned on the same vectors, run on the CPU) at ViT-B/16 shape.  Tolerances: fp32 token stream with 16 mantissa bits per GEMM operand and fp32

@@ -1,4 +1,5 @@
-"""-m gpu: the native CLIP image tower (hedit_clipimg_* of csrc/clipimg.hip behind hedit.clip_score.NativeClipImage), the
+"""-m gpu: the native CLIP image tower (hedit_clipimg_* of csrc/clipimg.hip on the shared encoder kernels and block forward of
+csrc/encoder.hip / encoder.h, behind hedit.clip_score.NativeClipImage), the
 CLIP score on top of it and the evaluator's clip_similarity_* columns, against tests/golden/g20_clipimg.npz -- vectors
 recorded by RUNNING the reference's ``CLIP`` and transformers' CLIPModel (tests/golden/make_golden_clipimg.py; pinned on
 the host by tests/test_host_clip_score.py).

@@ -1,4 +1,5 @@
-"""-m gpu: the native DINO ViT key extractor and the key self-similarity distance (hedit_dino_* of csrc/dino.hip behind
+"""-m gpu: the native DINO ViT key extractor and the key self-similarity distance (hedit_dino_* of csrc/dino.hip on the shared encoder
+kernels and block forward of csrc/encoder.hip / encoder.h, behind
 hedit.dino_score.NativeDinoStructure) and the evaluator's structure_distance columns, on seeded stand-in weights with chosen
 scales (DinoNet.init_random), against the fp64 torch restatement tests/helpers/dino_ref.py run on the CPU.  PARITY UNPINNED
 against the published network: no DINO code or weights exist offline and the reference tree holds no vector for this metric;

@@ -1,4 +1,5 @@
-"""-m gpu: the native prompt encoder (hedit_text_* of csrc/text.hip behind hedit.text.NativeClipText; SURVEY.md section 8
+"""-m gpu: the native prompt encoder (hedit_text_* of csrc/text.hip on the shared encoder kernels and block forward of
+csrc/encoder.hip / encoder.h, behind hedit.text.NativeClipText; SURVEY.md section 8
 row a7) against tests/golden/g19_text.npz -- vectors recorded by RUNNING the reference's ``CLIP.encode_text`` and
 transformers' CLIPTextModel (tests/golden/make_golden_text.py; pinned on the host by tests/test_host_text.py).
 

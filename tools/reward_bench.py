@@ -14,6 +14,9 @@ from hedit.arcface import IDLoss  # noqa: E402
 from hedit.arcface.lpips_loss import LPIPS_Loss  # noqa: E402
 from hedit.clip_guidance import CLIPEncoder  # noqa: E402
 from hedit.clip_guidance.base_clip import ClipVisualPrefix  # noqa: E402
+from hedit import _lib  # noqa: E402
+if os.environ.get("HEDIT_LIB_VARIANT"):       # tools/build_variant.sh side library (A/B runs inside one GPU call)
+    _lib.LIB_PATH = os.path.join(os.path.dirname(_lib.LIB_PATH), f"lib_{os.environ['HEDIT_LIB_VARIANT']}.so.bin")
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 dev = torch.device("cuda:0")
