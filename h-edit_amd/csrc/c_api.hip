@@ -510,6 +510,25 @@ int hedit_k_cross_attn_bwd_q(const void* q, int ldq, const void* k, int ldk, con
   return attn_bwd_launch(p, S(stream));
 } catch (...) { return hedit_abi_catch(); }
 
+size_t hedit_k_cross_attn_bwd_kv_ws_bytes(int B, int N, int heads, int d) {
+  if (B < 1 || N < 1 || heads < 1 || d < 1) return 0;
+  return attn_bwd_ws_bytes(B, N, heads) + attn_bwd_ctx_kv_ws_bytes(B, N, heads, d);
+}
+
+int hedit_k_cross_attn_bwd_kv(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o, int ldo,
+                              const void* dout, int lddo, void* dk, void* dv, int lddkv, int B, int N, int heads, int d, void* ws,
+                              void* stream) try {
+  ARG_CHECK(q && k && v && o && dout && dk && dv && ws, "cross_attn_bwd_kv args");
+  ARG_CHECK(reinterpret_cast<uintptr_t>(ws) % 16 == 0, "cross_attn_bwd_kv: the workspace must be 16-byte aligned");
+  AttnBwdParams p = attn_bwd_params(q, ldq, k, ldk, v, ldv, o, ldo, dout, lddo, nullptr, 0, B, N, heads, d);
+  p.M = HEDIT_MAXW; p.kstride = HEDIT_CTXP;
+  p.stats = reinterpret_cast<float*>(ws);
+  const int rc = attn_bwd_launch(p, S(stream));      // (lse, delta) per query; no dq
+  if (rc != HEDIT_OK) return rc;
+  p.dk = reinterpret_cast<bf16_t*>(dk); p.dv = reinterpret_cast<bf16_t*>(dv); p.lddkv = lddkv;
+  return attn_bwd_ctx_kv_launch(p, p.stats + attn_bwd_ws_bytes(B, N, heads) / sizeof(float), S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
 int hedit_k_groupnorm_bwd_any(const void* x, const void* dy, const void* add, void* dx, const float* gamma, const float* beta,
                               const float* stats, int B, int HW, int C, int G, int silu, void* ws, void* stream) try {
   ARG_CHECK(x && dy && dx && gamma && beta && stats && ws, "groupnorm_bwd_any args");

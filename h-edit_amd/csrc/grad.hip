@@ -357,12 +357,12 @@ __global__ __launch_bounds__(256) void pack_conv3x3_dgrad_kernel(const float* __
   }
 }
 // [O][I] fp32 -> bf16 [I][O]
-__global__ __launch_bounds__(256) void pack_linear_t_kernel(const float* __restrict__ w, bf16_t* __restrict__ out, int O, int I, float scale) {
+__global__ __launch_bounds__(256) void pack_linear_t_kernel(const float* __restrict__ w, bf16_t* __restrict__ out, int O, int I, float scale, long ldo) {
   const long total = (long)O * I;
   for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
     const int o = (int)(idx % O);
     const int i = (int)(idx / O);
-    out[idx] = f32_to_bf16(w[(long)o * I + i] * scale);
+    out[i * ldo + o] = f32_to_bf16(w[(long)o * I + i] * scale);
   }
 }
 // OIHW fp32 (k x k) -> IOHW fp32 with the taps flipped (k = 1: a plain transpose)
@@ -447,8 +447,8 @@ int pack_conv3x3_dgrad_launch(const float* w_oihw, bf16_t* out, int O, int I, hi
   return HEDIT_OK;
 }
 
-int pack_linear_t_launch(const float* w, bf16_t* out, int O, int I, hipStream_t st, float scale) {
-  hipLaunchKernelGGL(pack_linear_t_kernel, dim3(ew_grid((long)O * I)), dim3(256), 0, st, w, out, O, I, scale);
+int pack_linear_t_launch(const float* w, bf16_t* out, int O, int I, hipStream_t st, float scale, long ldo) {
+  hipLaunchKernelGGL(pack_linear_t_kernel, dim3(ew_grid((long)O * I)), dim3(256), 0, st, w, out, O, I, scale, ldo > 0 ? ldo : (long)O);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }

@@ -191,7 +191,8 @@ int sum2x2_launch(const bf16_t* du, bf16_t* dx, int B, int H, int W, int C, hipS
 // weights of the input-gradient GEMMs: conv3x3 OIHW -> bf16 [I][9][O] taps flipped; linear [O][I] -> bf16 [I][O];
 // k x k OIHW fp32 -> IOHW fp32 taps flipped
 int pack_conv3x3_dgrad_launch(const float* w_oihw, bf16_t* out, int O, int I, hipStream_t st);
-int pack_linear_t_launch(const float* w, bf16_t* out, int O, int I, hipStream_t st, float scale = 1.f);   // out = (scale * w)^T
+// out = (scale * w)^T, [I][ldo] (ldo = 0: dense, O)
+int pack_linear_t_launch(const float* w, bf16_t* out, int O, int I, hipStream_t st, float scale = 1.f, long ldo = 0);
 int flip_oihw_launch(const float* w, float* out, int O, int I, int k, hipStream_t st);
 // LayerNorm backward over rows of width C (C % 8 == 0, C <= 1536): mean / rstd recomputed from the kept x; dx (+ add, if given)
 int layernorm_bwd_launch(const bf16_t* x, const bf16_t* dy, const bf16_t* add, bf16_t* dx, const float* gamma, long rows, int C,
@@ -272,7 +273,12 @@ struct AttnBwdParams {
   int B, N, M, kstride, heads, d;
 };
 size_t attn_bwd_ws_bytes(int B, int N, int heads);
-int attn_bwd_launch(const AttnBwdParams& p, hipStream_t st);
+int attn_bwd_launch(const AttnBwdParams& p, hipStream_t st);   // dq null: the statistics only
+// dk / dv of the context form (M keys of HEDIT_CTXP rows per image; dk, dv [B*HEDIT_CTXP][lddkv], rows >= M exact zeros) from the
+// statistics of attn_bwd_launch: fp32 partials per query chunk (a function of N only) in `part`, summed in ascending order
+int attn_bwd_ctx_chunk(int N);
+size_t attn_bwd_ctx_kv_ws_bytes(int B, int N, int heads, int d);
+int attn_bwd_ctx_kv_launch(const AttnBwdParams& p, float* part, hipStream_t st);
 
 // ---------------------------------------------------------------- step.hip
 struct StepCoef {

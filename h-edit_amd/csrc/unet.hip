@@ -41,7 +41,7 @@ struct Slot {
   // the chain width the unfused forward weights).  kind: 0 fp32 copy, 1 linear -> bf16 (scaled), 10 linear [O][I] -> bf16 [I][O]
   // (scaled), 11 conv3x3 -> bf16 [I][9][O] taps flipped, 12 the same with the taps in place (stride-2 dgrad), 13 OIHW -> fp32
   // IOHW taps flipped
-  struct Extra { int kind; void* dst; float scale; int O, I; };
+  struct Extra { int kind; void* dst; float scale; int O, I; long ld = 0; };      // ld: row stride of a kind-10 destination (0 = dense)
   std::vector<Extra> extra;
 };
 
@@ -121,6 +121,9 @@ struct hedit_unet {
   float *conv_out_t = nullptr, *zero_bias = nullptr;
   void* tape = nullptr;
   void (*tape_free)(void*) = nullptr;
+  // hedit_unet_create_grad_ctx only: [wk2_all | wv2_all]^T as [cross_attention_dim][2 * ctx_n] -- block b's to_k^T at columns
+  // ctx_off .., its to_v^T at ctx_n + ctx_off .. -- the weight of the one GEMM that turns every dK / dV into d_ctx
+  bf16_t* wkv2_t = nullptr;
 };
 
 namespace {
@@ -268,7 +271,15 @@ Attn make_attn(hedit_unet* h, const std::string& pre, int C) {
   a.ctx_off = h->ctx_next;
   h->ctx_next += C;
   a.w_k2 = linp(h, tb + ".attn2.to_k.weight", C, ctx, h->wk2_all + (size_t)a.ctx_off * ctx);
+  if (h->wkv2_t) {
+    add_extra<bf16_t>(h, 10, h->wkv2_t + a.ctx_off, (size_t)C * ctx, C, ctx);
+    h->slots.back().extra.back().ld = 2L * h->ctx_n;
+  }
   a.w_v2 = linp(h, tb + ".attn2.to_v.weight", C, ctx, h->wv2_all + (size_t)a.ctx_off * ctx);
+  if (h->wkv2_t) {
+    add_extra<bf16_t>(h, 10, h->wkv2_t + h->ctx_n + a.ctx_off, (size_t)C * ctx, C, ctx);
+    h->slots.back().extra.back().ld = 2L * h->ctx_n;
+  }
   if (chain) {
     stream_slot(tb + ".attn2.to_out.0.weight", a.ffs, 0, 0, C, C, 1.f, 2);
   } else {
@@ -970,7 +981,8 @@ int forward_impl(hedit_unet* h, const float* x, float t, const float* ctx, int B
 
 // =============================================================================== C ABI
 // grad: attach the input-gradient twins (hedit_unet_create_grad); without it, exactly the forward-only handle
-static int create_impl(const hedit_unet_cfg* cfg, hedit_unet** out, bool grad) {
+// ctx: also the transposed context projections (hedit_unet_create_grad_ctx)
+static int create_impl(const hedit_unet_cfg* cfg, hedit_unet** out, bool grad, bool ctx = false) {
   ARG_CHECK(cfg && out, "null");
   ARG_CHECK(cfg->n_levels >= 2 && cfg->n_levels <= HEDIT_MAX_LEVELS, "n_levels");
   ARG_CHECK(cfg->in_channels <= 8 && cfg->out_channels <= 4, "in/out channels");
@@ -1025,6 +1037,7 @@ static int create_impl(const hedit_unet_cfg* cfg, hedit_unet** out, bool grad) {
   h->ctx_n += ch[n - 1];
   h->wk2_all = dalloc<bf16_t>(h, (size_t)h->ctx_n * cfg->cross_attention_dim);
   h->wv2_all = dalloc<bf16_t>(h, (size_t)h->ctx_n * cfg->cross_attention_dim);
+  if (ctx) h->wkv2_t = dalloc<bf16_t>(h, (size_t)2 * h->ctx_n * cfg->cross_attention_dim);
 
   int toff = 0;
   int outc = ch[0];
@@ -1103,6 +1116,7 @@ static int create_impl(const hedit_unet_cfg* cfg, hedit_unet** out, bool grad) {
     delete h;
     return HEDIT_ERR_STATE;
   }
+  if (ctx && !h->wkv2_t) { hedit_set_error("hipMalloc failed for the transposed context projections"); return HEDIT_ERR_HIP; }
   for (void* p : h->owned)
     if (!p) { hedit_set_error("hipMalloc failed while creating the UNet"); return HEDIT_ERR_HIP; }
   for (auto& s : h->slots) {
@@ -1122,6 +1136,10 @@ int hedit_unet_create(const hedit_unet_cfg* cfg, hedit_unet** out) try {
 
 int hedit_unet_create_grad(const hedit_unet_cfg* cfg, hedit_unet** out) try {
   return create_impl(cfg, out, true);
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_unet_create_grad_ctx(const hedit_unet_cfg* cfg, hedit_unet** out) try {
+  return create_impl(cfg, out, true, true);
 } catch (...) { return hedit_abi_catch(); }
 
 void hedit_unet_destroy(hedit_unet* h) try {
@@ -1187,7 +1205,7 @@ int hedit_unet_load(hedit_unet* h, const char* name, const float* w, size_t nume
     bf16_t* d16 = reinterpret_cast<bf16_t*>(e.dst);
     if (e.kind == 0) HIP_TRY(hipMemcpyAsync(e.dst, w, numel * sizeof(float), hipMemcpyDeviceToDevice, st));
     else if (e.kind == 1) TRY(pack_linear_launch(w, d16, (long)numel, e.scale, st));
-    else if (e.kind == 10) TRY(pack_linear_t_launch(w, d16, e.O, e.I, st, e.scale));
+    else if (e.kind == 10) TRY(pack_linear_t_launch(w, d16, e.O, e.I, st, e.scale, e.ld));
     else if (e.kind == 11) TRY(pack_conv3x3_dgrad_launch(w, d16, e.O, e.I, st));
     else if (e.kind == 12) TRY(pack_conv3x3_s2_dgrad_launch(w, d16, e.O, e.I, st));
     else TRY(flip_oihw_launch(w, reinterpret_cast<float*>(e.dst), e.O, e.I, 3, st));
@@ -1277,6 +1295,10 @@ size_t hedit_unet_grad_workspace_bytes(hedit_unet* h, int B, int height, int wid
   float dummy = 0.f;   // never dereferenced in the dry run
   int rc = forward_keep_impl(h, T, nullptr, 0.f, nullptr, nullptr);
   if (rc == HEDIT_OK) rc = backward_impl(h, T, &dummy, &dummy);
+  if (h->wkv2_t) {      // the arena's peak is the largest of the three walks a context handle can be asked for
+    if (rc == HEDIT_OK) rc = backward_impl(h, T, &dummy, &dummy, &dummy);
+    if (rc == HEDIT_OK) rc = backward_impl(h, T, &dummy, nullptr, &dummy);
+  }
   return rc == HEDIT_OK ? T.f.ar.peak + 4096 : 0;
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
@@ -1312,6 +1334,28 @@ int hedit_unet_backward(hedit_unet* h, const float* d_eps, float* d_x, void* wor
   }
   T->f.st = reinterpret_cast<hipStream_t>(stream);
   const int rc = backward_impl(h, *T, d_eps, d_x);
+  if (rc != HEDIT_OK) drop_tape(h);   // a pass that stopped half way leaves temporaries in the arena
+  return rc;
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_unet_backward_ctx(hedit_unet* h, const float* d_eps, float* d_x, float* d_ctx, void* workspace, void* stream) try {
+  ARG_CHECK(h && d_eps && d_ctx && workspace, "null");
+  TRY(check_grad_handle(h, "hedit_unet_backward_ctx"));
+  if (!h->wkv2_t) {
+    hedit_set_error("hedit_unet_backward_ctx: this handle has no context-gradient weights (create it with hedit_unet_create_grad_ctx)");
+    return HEDIT_ERR_STATE;
+  }
+  if (!h->tape) {
+    hedit_set_error("hedit_unet_backward_ctx: no forward is being kept (call hedit_unet_forward_keep first)");
+    return HEDIT_ERR_STATE;
+  }
+  GradTape* T = reinterpret_cast<GradTape*>(h->tape);
+  if (T->ws != workspace) {
+    hedit_set_error("hedit_unet_backward_ctx: not the workspace the kept forward ran in");
+    return HEDIT_ERR_ARG;
+  }
+  T->f.st = reinterpret_cast<hipStream_t>(stream);
+  const int rc = backward_impl(h, *T, d_eps, d_x, d_ctx);
   if (rc != HEDIT_OK) drop_tape(h);   // a pass that stopped half way leaves temporaries in the arena
   return rc;
 } catch (...) { return hedit_abi_catch(); }

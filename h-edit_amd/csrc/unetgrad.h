@@ -6,8 +6,11 @@
 // keep nothing a backward could use) and records every block: a taped block takes its own GroupNorm statistics, a transformer
 // block keeps the inputs of its three LayerNorms, q | k, a row-major V, both attention outputs, the cross-attention query and
 // the FF1 pre-activation.  hedit_unet_backward walks the records in reverse; its temporaries go above / between the kept
-// buffers and are freed again, so any number of backward passes can follow one forward.  The gradient is with respect to x
-// only: nothing for the context, the timestep or the weights.
+// buffers and are freed again, so any number of backward passes can follow one forward.  hedit_unet_backward gives the
+// gradient with respect to x only.  hedit_unet_backward_ctx (a hedit_unet_create_grad_ctx handle) also forms dK / dV of every
+// cross-attention (attnbwd.hip, the context form) into the block's column slice of one [B*80][2 ctx_n] buffer [dK_all | dV_all],
+// and after the walk d_ctx = [dK_all | dV_all] [wk2_all | wv2_all] as one fp32 GEMM chain per element.  The forward is the same
+// for both; nothing for the timestep or the weights.
 #pragma once
 
 namespace {
@@ -198,7 +201,8 @@ int transformer_keep(Fwd& f, const Attn& a, const bf16_t* x, int H, int W, bf16_
 }
 
 // dy [M][C] -> *dx [M][C] (allocated here; dy is NOT freed).  v2: the tape's row-major attn2 values.
-int transformer_bwd(Fwd& f, const AttnTape& t, const bf16_t* v2_all, const bf16_t* dy, bf16_t** dx_out) {
+// dkv: null, or [B*80][2 ctx_n] = [dK_all | dV_all], whose column slices of this block are written.
+int transformer_bwd(Fwd& f, const AttnTape& t, const bf16_t* v2_all, const bf16_t* dy, bf16_t** dx_out, bf16_t* dkv = nullptr) {
   const Attn& a = *t.a;
   const int C = a.C, N = t.H * t.W, B = f.B, heads = f.h->cfg.heads, d = C / heads;
   const size_t M = (size_t)B * N;
@@ -227,7 +231,18 @@ int transformer_bwd(Fwd& f, const AttnTape& t, const bf16_t* v2_all, const bf16_
     p.q = t.q2; p.ldq = C; p.k = f.k2_all + a.ctx_off; p.ldk = f.h->ctx_n; p.v = v2_all + a.ctx_off; p.ldv = f.h->ctx_n;
     p.o = t.ao2; p.ldo = C; p.dout = dao; p.lddo = C; p.dq = dq2; p.lddq = C;
     p.B = B; p.N = N; p.M = HEDIT_MAXW; p.kstride = HEDIT_CTXP; p.heads = heads; p.d = d;
-    RUN(f, attn_bwd_launch(p, f.st));
+    if (dkv) {
+      float *st, *part;
+      TRY(aalloc(f, &st, attn_bwd_ws_bytes(B, N, heads) / sizeof(float)));
+      TRY(aalloc(f, &part, attn_bwd_ctx_kv_ws_bytes(B, N, heads, d) / sizeof(float)));
+      p.stats = st;
+      RUN(f, attn_bwd_launch(p, f.st));
+      p.dk = dkv + a.ctx_off; p.dv = dkv + f.h->ctx_n + a.ctx_off; p.lddkv = 2 * f.h->ctx_n;
+      RUN(f, attn_bwd_ctx_kv_launch(p, part, f.st));
+      f.ar.free(part); f.ar.free(st);
+    } else {
+      RUN(f, attn_bwd_launch(p, f.st));
+    }
   }
   TRY(linear(f, dq2, Mi, C, a.wq2_t, C, nullptr, nullptr, dtn, C));
   f.ar.free(dq2);
@@ -406,22 +421,28 @@ int add_pending(Fwd& f, bf16_t* d, bf16_t*& pend, const SkipRec& s) {
   return HEDIT_OK;
 }
 
-int block_bwd(Fwd& f, const GradTape& T, const BlkRec& br, bf16_t** d) {
+int block_bwd(Fwd& f, const GradTape& T, const BlkRec& br, bf16_t** d, bf16_t* dkv = nullptr, bool attn_only = false) {
   bf16_t* dx;
   if (br.has_attn) {
-    TRY(transformer_bwd(f, br.a, T.v2_all, *d, &dx));
+    TRY(transformer_bwd(f, br.a, T.v2_all, *d, &dx, dkv));
     f.ar.free(*d);
     *d = dx;
   }
+  if (attn_only) return HEDIT_OK;
   TRY(resblock_bwd(f, br.r, *d, &dx));
   f.ar.free(*d);
   *d = dx;
   return HEDIT_OK;
 }
 
-// d_x = (d eps / d x)^T d_eps from a tape made by forward_keep_impl; the tape is left as it was
-int backward_impl(hedit_unet* h, GradTape& T, const float* d_eps, float* d_x) {
+// d_x = (d eps / d x)^T d_eps from a tape made by forward_keep_impl; the tape is left as it was.  d_ctx (or null): also
+// (d eps / d ctx)^T d_eps, fp32 [B][77][cross_attention_dim]; d_x may then be null, and the walk ends above the first
+// transformer block of the down path (its ResBlock and conv_in feed d_x alone).
+int backward_impl(hedit_unet* h, GradTape& T, const float* d_eps, float* d_x, float* d_ctx = nullptr) {
   Fwd& f = T.f;
+  bf16_t* dkv = nullptr;
+  const int MC = f.B * HEDIT_CTXP;
+  if (d_ctx) TRY(aalloc(f, &dkv, (size_t)MC * 2 * h->ctx_n));
   const int B = f.B;
   hipStream_t st = f.st;
   const hedit_unet_cfg& c = h->cfg;
@@ -454,7 +475,7 @@ int backward_impl(hedit_unet* h, GradTape& T, const float* d_eps, float* d_x) {
     }
     for (size_t j = blk.res.size(); j-- > 0;) {
       const BlkRec& br = T.up[--ui];
-      TRY(block_bwd(f, T, br, &d));                 // d: [M][left + right]
+      TRY(block_bwd(f, T, br, &d, dkv));            // d: [M][left + right]
       const long M = (long)B * H * W;
       const int ld = br.left + br.right;
       bf16_t* dl;
@@ -472,7 +493,7 @@ int backward_impl(hedit_unet* h, GradTape& T, const float* d_eps, float* d_x) {
     bf16_t* dx;
     TRY(resblock_bwd(f, T.m2, d, &dx));
     f.ar.free(d);
-    TRY(transformer_bwd(f, T.ma, T.v2_all, dx, &d));
+    TRY(transformer_bwd(f, T.ma, T.v2_all, dx, &d, dkv));
     f.ar.free(dx);
     TRY(resblock_bwd(f, T.m1, d, &dx));
     f.ar.free(d);
@@ -482,7 +503,14 @@ int backward_impl(hedit_unet* h, GradTape& T, const float* d_eps, float* d_x) {
   TRY(add_pending(f, d, pend[k], T.hs[k]));
   // down path: the consumer on the down path first, then the pending gradient of the up path
   size_t di = T.down.size();
-  for (int i = n - 1; i >= 0; --i) {
+  long stop = -1;                 // without d_x: the first executed block with a transformer is the last one visited
+  if (!d_x) {
+    stop = (long)T.down.size();
+    for (size_t j = 0; j < T.down.size(); ++j)
+      if (T.down[j].has_attn) { stop = (long)j; break; }
+  }
+  bool done = !d_x && stop == (long)T.down.size();      // no transformer on the down path at all
+  for (int i = n - 1; i >= 0 && !done; --i) {
     const Block& blk = h->down[i];
     if (blk.has_sampler) {
       --k;
@@ -494,14 +522,20 @@ int backward_impl(hedit_unet* h, GradTape& T, const float* d_eps, float* d_x) {
       d = dx;
       TRY(add_pending(f, d, pend[k], s));
     }
-    for (size_t j = blk.res.size(); j-- > 0;) {
-      TRY(block_bwd(f, T, T.down[--di], &d));
+    for (size_t j = blk.res.size(); j-- > 0 && !done;) {
+      --di;
+      done = (long)di == stop;
+      TRY(block_bwd(f, T, T.down[di], &d, dkv, done));
+      if (done) break;
       --k;
       TRY(add_pending(f, d, pend[k], T.hs[k]));
     }
   }
+  if (done)
+    for (bf16_t*& q : pend)
+      if (q) { f.ar.free(q); q = nullptr; }
   // conv_in: the N = 4 route of the head convolution with the flipped, transposed weight
-  {
+  if (d_x) {
     float* prod;
     const size_t M = (size_t)B * T.H0 * T.W0;
     TRY(aalloc(f, &prod, M * 4));
@@ -513,6 +547,20 @@ int backward_impl(hedit_unet* h, GradTape& T, const float* d_eps, float* d_x) {
     f.ar.free(prod);
   }
   f.ar.free(d);
+  if (d_ctx) {
+    // d_ctx = dK_all wk2_all + dV_all wv2_all: K = 2 ctx_n in one fp32 chain (raw products: no split, no 16-bit rounding)
+    const int dim = h->cfg.cross_attention_dim;
+    float* prod;
+    TRY(aalloc(f, &prod, (size_t)MC * dim));
+    GemmParams p{};
+    p.mode = 0; p.A = dkv; p.W = h->wkv2_t; p.M = MC; p.N = dim; p.K = 2 * h->ctx_n; p.lda = 2 * h->ctx_n; p.raw_f32 = prod; p.ldc = dim;
+    TRY(run_gemm(f, p));
+    if (!f.dry())
+      HIP_TRY(hipMemcpy2DAsync(d_ctx, (size_t)HEDIT_MAXW * dim * sizeof(float), prod, (size_t)HEDIT_CTXP * dim * sizeof(float),
+                               (size_t)HEDIT_MAXW * dim * sizeof(float), (size_t)f.B, hipMemcpyDeviceToDevice, st));
+    f.ar.free(prod);
+    f.ar.free(dkv);
+  }
   return HEDIT_OK;
 }
 

@@ -89,6 +89,8 @@ _SIGS = {
     "hedit_unet_forward_keep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.c_void_p, C.c_size_t, C.c_void_p]),
     "hedit_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hedit_unet_create_grad_ctx": (C.c_int, [C.POINTER(UnetCfg), C.POINTER(C.c_void_p)]),
+    "hedit_unet_backward_ctx": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "hedit_unet_release": (None, [C.c_void_p]),
     "hedit_unet_vjp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -323,6 +325,8 @@ _SIGS = {
     "hedit_k_attn_bwd_ws_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hedit_k_attn_bwd": (C.c_int, [C.c_void_p, C.c_int] * 6 + [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     "hedit_k_cross_attn_bwd_q": (C.c_int, [C.c_void_p, C.c_int] * 6 + [C.c_int] * 4 + [C.c_void_p]),
+    "hedit_k_cross_attn_bwd_kv_ws_bytes": (C.c_size_t, [C.c_int] * 4),
+    "hedit_k_cross_attn_bwd_kv": (C.c_int, [C.c_void_p, C.c_int] * 5 + [C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
     "hedit_k_layernorm_bwd": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_float, C.c_void_p]),
     "hedit_k_groupnorm_bwd_any": (C.c_int, [C.c_void_p] * 7 + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
     "hedit_k_geglu_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),

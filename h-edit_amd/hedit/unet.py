@@ -20,6 +20,10 @@ probabilities through HBM), same protocol.
 whenever grad mode is on and ``sample.requires_grad``, a PLAIN pass (``use_controller=False`` or no controller registered,
 no attention editor) is an autograd node whose backward is the executor's input-gradient pass -- what Noise Map Guidance
 differentiates (text-guided/inversion/p2p_baselines.py:251-268).  The gradient is with respect to the sample only.
+
+``grad="context"`` builds the handle of hedit_unet_create_grad_ctx instead: the same node then also answers for
+``encoder_hidden_states`` when that requires grad (hedit_unet_backward_ctx) -- what null-text inversion optimises
+(text-guided/inversion/pnp_baselines.py:134-236).  Nothing else changes; ``grad=True`` still refuses such a context.
 """
 import ctypes as C
 import hashlib
@@ -82,15 +86,17 @@ def random_state_dict(param_shapes, seed=0):
 
 class _EpsGrad(torch.autograd.Function):
     """eps = unet(sample, t, ctx) with the forward's tape kept in the model's gradient workspace; backward = the executor's
-    vector-Jacobian product.  The tape stays until the model's next call, so ``retain_graph=True`` and a second backward
+    vector-Jacobian product with respect to whichever of (sample, ctx) ``needs_input_grad`` asks for (ctx: a
+    ``grad="context"`` model, hedit_unet_backward_ctx).  The tape stays until the model's next call, so ``retain_graph=True`` and a second backward
     work; a backward after the model has run again is an error, not another forward's gradient (the ticket check of
     hedit/diffusion/diffusion.py)."""
 
     @staticmethod
-    def forward(ctx, sample, model, t, enc):
+    def forward(ctx, sample, enc, model, t):
         ctx.model = model
         ctx.ticket, eps = model._keep(sample.detach(), t, enc)
         ctx.shape = sample.shape
+        ctx.enc_shape = enc.shape
         return eps
 
     @staticmethod
@@ -99,10 +105,16 @@ class _EpsGrad(torch.autograd.Function):
         if m._ticket != ctx.ticket:
             raise RuntimeError("hedit.UNet2DConditionModel: the kept forward of this graph was dropped by a later model call")
         g = g.detach().to(dtype=torch.float32).contiguous()
-        dx = torch.empty(ctx.shape, dtype=torch.float32, device=m.device)
+        want_x, want_c = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        dx = torch.empty(ctx.shape, dtype=torch.float32, device=m.device) if want_x else None
+        dc = torch.empty(ctx.enc_shape, dtype=torch.float32, device=m.device) if want_c else None
         with torch.cuda.device(m.device):
-            _lib.check(m._lib.hedit_unet_backward(m._h, _lib.ptr(g), _lib.ptr(dx), _lib.ptr(m._gws), _lib.cur_stream()))
-        return dx, None, None, None
+            if want_c:
+                _lib.check(m._lib.hedit_unet_backward_ctx(m._h, _lib.ptr(g), _lib.ptr(dx) if want_x else None, _lib.ptr(dc),
+                                                          _lib.ptr(m._gws), _lib.cur_stream()))
+            elif want_x:
+                _lib.check(m._lib.hedit_unet_backward(m._h, _lib.ptr(g), _lib.ptr(dx), _lib.ptr(m._gws), _lib.cur_stream()))
+        return dx, dc, None, None
 
 
 class UNet2DConditionModel:
@@ -133,10 +145,14 @@ class UNet2DConditionModel:
         self._cfg_struct = c
         h = C.c_void_p()
         with torch.cuda.device(self.device):
-            create = self._lib.hedit_unet_create_grad if grad else self._lib.hedit_unet_create
+            if isinstance(grad, str) and grad != "context":
+                raise ValueError(f'grad must be False, True or "context", got {grad!r}')
+            create = (self._lib.hedit_unet_create_grad_ctx if grad == "context" else
+                      self._lib.hedit_unet_create_grad if grad else self._lib.hedit_unet_create)
             _lib.check(create(C.byref(c), C.byref(h)))
         self._h = h
         self.grad = bool(grad)
+        self.grad_context = grad == "context"      # the handle also differentiates encoder_hidden_states
         self._ticket = 0          # identifies the kept forward; 0 = none
         self._gws = None          # the tape's workspace (hedit_unet_grad_workspace_bytes)
         self.param_shapes = {}
@@ -414,15 +430,17 @@ class UNet2DConditionModel:
             controller = getattr(self, "_attention_editor", None)
         if self.grad:
             self._release()
-            if torch.is_grad_enabled() and encoder_hidden_states.requires_grad:
+            ctx_grad = torch.is_grad_enabled() and encoder_hidden_states.requires_grad
+            if ctx_grad and not self.grad_context:
                 raise NotImplementedError("the gradient with respect to encoder_hidden_states (null-text inversion) is not "
-                                          "implemented: the input-gradient pass differentiates the sample only")
-            if torch.is_grad_enabled() and sample.requires_grad:
+                                          "implemented on this model: the input-gradient pass of grad=True differentiates the "
+                                          "sample only (build the model with grad=\"context\")")
+            if torch.is_grad_enabled() and (sample.requires_grad or ctx_grad):
                 if controller is not None:
                     what = "an attention editor" if controller is getattr(self, "_attention_editor", None) else "a registered controller"
                     raise NotImplementedError(f"{what} is in the way: the input-gradient pass differentiates the plain network "
                                               "only (pass cross_attention_kwargs={'use_controller': False, 'use_editor': False})")
-                return UNetOutput(sample=_EpsGrad.apply(sample, self, t, ctx))
+                return UNetOutput(sample=_EpsGrad.apply(sample, ctx, self, t))
         from .p2p.ptp_classes import runs_in_python
         if runs_in_python(controller):
             return UNetOutput(sample=self.forward_hooked(sample, t, ctx, controller, save_attn))

@@ -195,7 +195,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.mode in _NEEDS_GRADIENT:
         raise NotImplementedError(f"mode {args.mode}: needs the gradient of a UNet pass with respect to its input (noise-map "
-                                  "guidance / null-text optimisation), which this driver does not build; the nmg modes run in main_nmg.py")
+                                  "guidance / null-text optimisation), which this driver does not build; the nmg modes run in main_nmg.py, nt_pnp in main_nt.py")
     if args.mode in _REFERENCE_ASSERTS:
         raise NotImplementedError(f"mode {args.mode}: the reference's ef_or_pnp_inv_w_pnp asserts etas == 0 while its driver passes "
                                   "1.0, so the reference mode cannot run as shipped; the function is in hedit.inversion.pnp_baselines")

@@ -17,8 +17,8 @@ that name it raises NotImplementedError (:262).  Running it is a deliberate diff
 
 Dataset format, image loading, controller / injection set-up and the output sub-directory follow the reference driver of the
 mode's family, as in main_baselines.py, whose machinery this driver uses; main_baselines.py itself keeps refusing these names.
-``nt_pnp`` stays refused: null-text inversion needs the gradient with respect to the text context, which the input-gradient
-pass does not form.  Additions as in main_p2p.py: ``--model_path`` / ``--random_init`` / ``--tiny`` / ``--seed``, sharding
+``nt_pnp`` stays refused here: null-text inversion needs the gradient with respect to the text context, which the
+input-gradient pass of ``grad=True`` does not form; it runs in main_nt.py over ``grad="context"``.  Additions as in main_p2p.py: ``--model_path`` / ``--random_init`` / ``--tiny`` / ``--seed``, sharding
 over ranks under torch.distributed.run, ``--batch N`` (N entries in lock-step, the L1 mean per image: same bits per image as
 one at a time)."""
 import calendar
@@ -122,7 +122,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.mode == "nt_pnp":
         raise NotImplementedError("mode nt_pnp: null-text inversion optimises the unconditional embedding, i.e. it needs the gradient "
-                                  "with respect to the text context, which the UNet's input-gradient pass does not form")
+                                  "with respect to the text context, which the UNet's input-gradient pass of this driver does not "
+                                  "form; the mode runs in main_nt.py")
     if args.mode not in MODES:
         where = "main_baselines.py" if args.mode in BASELINE_MODES else "the h-Edit drivers"
         raise NotImplementedError(f"mode {args.mode}: this driver runs {', '.join(MODES)}; see {where}")

@@ -179,8 +179,18 @@ int hedit_unet_store_layer_info(const hedit_unet* h, int height, int width, int 
  * hedit_unet_backward: one pass over the tape, which it leaves intact (any number of cotangents per forward; the same bits
  *   each time).  d_eps fp32 [B][Cout][H][W] -> d_x fp32 [B][Cin][H][W].  Batch rows are the bits of single calls.
  * hedit_unet_vjp: both in one call, nothing kept.
+ * hedit_unet_create_grad_ctx: hedit_unet_create_grad whose load also fills [wk2_all | wv2_all]^T, the transposed stack of
+ *   every block's attn2.to_k / to_v ([cross_attention_dim][2 * sum of the blocks' widths]) -- what the gradient with respect
+ *   to the TEXT CONTEXT needs (null-text inversion).  hedit_unet_grad_workspace_bytes on such a handle also covers
+ *   hedit_unet_backward_ctx; on a hedit_unet_create_grad handle it is what it was.
+ * hedit_unet_backward_ctx: hedit_unet_backward over the same tape that also forms dK / dV of every cross-attention
+ *   (csrc/attnbwd.hip, the context form) and from them d_ctx fp32 [B][77][cross_attention_dim] in ONE fp32 GEMM chain per
+ *   element (never rounded to 16 bits).  d_x may be NULL: the walk then stops above the first transformer block; d_ctx has
+ *   the same bits either way, d_x the bits of hedit_unet_backward.  HEDIT_ERR_STATE on a handle without the context weights.
  * HEDIT_ERR_STATE: a forward-only handle, a backward without a tape, or a set attention hook. */
 int hedit_unet_create_grad(const hedit_unet_cfg* cfg, hedit_unet** out);
+int hedit_unet_create_grad_ctx(const hedit_unet_cfg* cfg, hedit_unet** out);
+int hedit_unet_backward_ctx(hedit_unet* h, const float* d_eps, float* d_x, float* d_ctx, void* workspace, void* stream);
 size_t hedit_unet_grad_workspace_bytes(hedit_unet* h, int B, int height, int width);
 int hedit_unet_forward_keep(hedit_unet* h, const float* x, float t, const float* ctx, int B, int height, int width, float* eps,
                             void* workspace, size_t workspace_bytes, void* stream);
@@ -483,6 +493,11 @@ int hedit_k_slice_add(const void* src, int ld, int off, int c, void* dst, int64_
  *   160}, N % 64 == 0, every row stride a multiple of 8 and >= heads*d.
  * hedit_k_cross_attn_bwd_q: the query gradient of the attention over the 77 context rows (k, v [B*80][ld]; rows 77 .. 79 of an
  *   image are never read); the context is not differentiated.
+ * hedit_k_cross_attn_bwd_kv: the other half, dk and dv [B*80][lddkv] at head column h*d (dk with respect to the unscaled k).
+ *   The queries are split into chunks whose length depends on N alone (128; the last may be shorter): a block per (image,
+ *   head, chunk) writes an fp32 partial, a second kernel sums the chunks in ascending order and rounds once -- no atomics,
+ *   batch rows are the bits of single calls.  Rows 77 .. 79 of k, v are never read; those rows of dk, dv are written as exact
+ *   zeros.  ws of hedit_k_cross_attn_bwd_kv_ws_bytes (16-byte aligned): the (lse, delta) statistics, then the partials.
  * hedit_k_layernorm_bwd: dx = d LayerNorm(x) / dx applied to dy (+ add, or NULL, summed in fp32 with one rounding); mean and
  *   rstd recomputed from x in fp32.  C % 8 == 0, C <= 1536.
  * hedit_k_geglu_bwd: x = [value | gate] [rows][2 inner] as hedit_k_geglu takes it, dy [rows][inner] the gradient of
@@ -498,6 +513,10 @@ int hedit_k_attn_bwd(const void* q, int ldq, const void* k, int ldk, const void*
                      void* ws, void* stream);
 int hedit_k_cross_attn_bwd_q(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o, int ldo,
                              const void* dout, int lddo, void* dq, int lddq, int B, int N, int heads, int d, void* stream);
+size_t hedit_k_cross_attn_bwd_kv_ws_bytes(int B, int N, int heads, int d);
+int hedit_k_cross_attn_bwd_kv(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const void* o, int ldo,
+                              const void* dout, int lddo, void* dk, void* dv, int lddkv, int B, int N, int heads, int d, void* ws,
+                              void* stream);
 int hedit_k_layernorm_bwd(const void* x, const void* dy, const void* add, void* dx, const float* gamma, int64_t rows, int C,
                           float eps, void* stream);
 int hedit_k_groupnorm_bwd_any(const void* x, const void* dy, const void* add, void* dx, const float* gamma, const float* beta,
