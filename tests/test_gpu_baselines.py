@@ -47,6 +47,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 from helpers import baseline_ref as BR  # noqa: E402
 from helpers import gpu as G  # noqa: E402
+from helpers.datasets import pie_dataset as _dataset  # noqa: E402
 from helpers.models import make_pair  # noqa: E402
 from helpers.tiny import PROMPT_PAIRS, TINY4_CONFIG, ddim_tables  # noqa: E402
 from hedit import _lib  # noqa: E402
@@ -411,25 +412,6 @@ def _driver():
     m = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(m)
     return m
-
-
-def _dataset(tmp_path):
-    from PIL import Image
-    d = tmp_path / "data"
-    (d / "annotation_images" / "0_random").mkdir(parents=True)
-    y, x = np.mgrid[0:96, 0:128]
-    mapping = {}
-    for i, (src, tar, blend, cat) in enumerate([("a cat sitting on a bench", "a dog sitting on a bench", "cat dog", "0"),
-                                                 ("a [red] car", "a [blue] car on a road", "", "1"),
-                                                 ("a tree", "a tall tree", "tree tree", "7")]):
-        img = np.stack([(x * (i + 2)) % 256, (y * 3 + i * 40) % 256, (x + y) % 256], -1).astype(np.uint8)
-        rel = f"0_random/{i:012d}.png"
-        Image.fromarray(img).save(d / "annotation_images" / rel)
-        mapping[f"{i:012d}"] = dict(image_path=rel, original_prompt=src, editing_prompt=tar, editing_instruction="",
-                                    editing_type_id=cat, blended_word=blend)
-    with open(d / "mapping_file.json", "w") as f:
-        json.dump(mapping, f)
-    return d
 
 
 MODE_FLAGS = {"ef": ["--eta", "1.0", "--skip", "1"], "ef_p2p": ["--eta", "1.0"], "pnp_inv_p2p": ["--eta", "0.0", "--sa", "0.6"],

@@ -377,7 +377,7 @@ def test_nt_driver_writes_edited_images(tmp_path):
     optimiser, one loss per image): byte-identical files; other modes are refused with the driver that runs them"""
     import numpy as np
     from PIL import Image
-    from test_gpu_baselines import _dataset
+    from helpers.datasets import pie_dataset as _dataset
     d = _dataset(tmp_path)
     common = ["--data_path", str(d), "--random_init", "--tiny", "--num_diffusion_steps", "4", "--edit_category_list", "0", "1",
               "--mode", "nt_pnp", "--pnp_f_t", "0.5", "--pnp_attn_t", "0.75"]

@@ -13,6 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "h-edit_amd"))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from helpers import gpu as G  # noqa: E402
+from helpers.datasets import pie_dataset as _dataset  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -22,25 +23,6 @@ def _driver():
     m = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(m)
     return m
-
-
-def _dataset(tmp_path):
-    from PIL import Image
-    d = tmp_path / "data"
-    (d / "annotation_images" / "0_random").mkdir(parents=True)
-    y, x = np.mgrid[0:96, 0:128]
-    mapping = {}
-    for i, (src, tar, blend, cat) in enumerate([("a cat sitting on a bench", "a dog sitting on a bench", "cat dog", "0"),
-                                                 ("a [red] car", "a [blue] car on a road", "", "1"),
-                                                 ("a tree", "a tall tree", "tree tree", "7")]):
-        img = np.stack([(x * (i + 2)) % 256, (y * 3 + i * 40) % 256, (x + y) % 256], -1).astype(np.uint8)
-        rel = f"0_random/{i:012d}.png"
-        Image.fromarray(img).save(d / "annotation_images" / rel)
-        mapping[f"{i:012d}"] = dict(image_path=rel, original_prompt=src, editing_prompt=tar, editing_instruction="",
-                                    editing_type_id=cat, blended_word=blend)
-    with open(d / "mapping_file.json", "w") as f:
-        json.dump(mapping, f)
-    return d
 
 
 @pytest.mark.parametrize("extra", [["--implicit", "--optimization_steps", "2"], [],

@@ -638,7 +638,7 @@ def test_nmg_driver_writes_edited_images(tmp_path, mode):
     image): byte-identical files"""
     import numpy as np
     from PIL import Image
-    from test_gpu_baselines import _dataset
+    from helpers.datasets import pie_dataset as _dataset
     d = _dataset(tmp_path)
     common = ["--data_path", str(d), "--random_init", "--tiny", "--num_diffusion_steps", "4", "--edit_category_list", "0", "1",
               "--mode", mode] + NMG_FLAGS[mode]
