@@ -121,6 +121,18 @@ int hedit_step_style(const float* e_u_src, const float* e_c_src, const float* e_
                            chain, weight, S(stream));
 } catch (...) { return hedit_abi_catch(); }
 
+int hedit_step_ef_seed(const float* g_z, float* d_eps, int n_img, int elems, float w_tar, float a, float c, void* stream) try {
+  ARG_CHECK(g_z && d_eps && n_img >= 1 && elems >= 1, "step_ef_seed args");
+  (void)a;      // the direct term a * g_z belongs to step_ef_style: the seed carries the path through eps only
+  return step_ef_seed_launch(g_z, d_eps, n_img, elems, w_tar, c, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_step_ef_style(const float* e_u, const float* e_c, int64_t stride_img, const float* dx, const float* g_z,
+                        const float* x_prev, float* x_out, int n_img, int elems, float a, float weight, void* stream) try {
+  ARG_CHECK(e_u && e_c && dx && g_z && x_prev && x_out && n_img >= 1 && elems >= 1, "step_ef_style args");
+  return step_ef_style_launch(e_u, e_c, (long)stride_img, dx, g_z, x_prev, x_out, n_img, elems, a, weight, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
 int hedit_local_blend(float* const* h_maps, int n_maps, int heads, const float* alpha_layers,
                       const int32_t* enabled, float* xt, int n_img, int C, int H, int W, float th, void* stream) try {
   ARG_CHECK(h_maps && alpha_layers && xt, "local_blend args");

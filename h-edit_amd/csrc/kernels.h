@@ -310,6 +310,12 @@ int step_tweedie_launch(const float* e_u_tar, const float* e_c_tar, long stride_
 int step_style_launch(const float* e_u_src, const float* e_c_src, const float* e_u_tar, const float* e_c_tar,
                       long stride_img, const float* x, const float* g_z, float* x_out, int n_img, int elems, float w_hat,
                       float w_tar, float chain, float weight, hipStream_t st);
+// style step of the Edit Friendly comparison editor (n-style ef.py:91-124), either side of the UNet's input-gradient pass:
+// the cotangent of the plain pass [n uncond | n cond] rows, d_eps_u = (1-w) c g_z, d_eps_c = w c g_z; and
+// x_out = x_prev - rho g with g = (dx_u + dx_c) + a g_z, rho = rms(e_c - e_u) / rms(g) * weight (per image; x_out may be x_prev)
+int step_ef_seed_launch(const float* g_z, float* d_eps, int n_img, int elems, float w_tar, float c, hipStream_t st);
+int step_ef_style_launch(const float* e_u, const float* e_c, long stride_img, const float* dx, const float* g_z,
+                         const float* x_prev, float* x_out, int n_img, int elems, float a, float weight, hipStream_t st);
 // out[o][i][x] = sum_j val[i][j] in[o][idx[i][j]][x] over a [outer][n_in][inner] fp32 tensor (tables [n_out][nnz])
 int axis_mix_launch(const float* in, float* out, const int* idx, const float* val, int nnz, long outer, int n_in, int n_out, int inner,
                     hipStream_t st);

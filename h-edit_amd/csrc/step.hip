@@ -274,7 +274,90 @@ __global__ __launch_bounds__(1024) void step_style_kernel(const float* __restric
   for (int i = threadIdx.x; i < elems; i += blockDim.x) x_out[(long)img * elems + i] = xi[i] - rho * (gi[i] * chain);
 }
 
+// ---- the style step of the Edit Friendly comparison editor (text-guided-n-style/inversion/ef.py:91-124): there the loss is
+// differentiated through the eps-network, x0 = (x - sqrt(1-ab) e(x)) / sqrt(ab) with e = e_u + w (e_c - e_u) from a plain
+// two-row pass [x|uncond, x|tar].  With a = inv_scale / sqrt(ab), c = -a sqrt(1-ab) and g_z = d loss / d (x0 * inv_scale):
+//   seed:  the cotangent of that pass in its row layout [n uncond rows | n cond rows]:  d_eps_u = (1-w) c g_z, d_eps_c = w c g_z
+//   style: g = (dx_u + dx_c) + a g_z with dx the rows of the UNet's input gradient; x_out = x_prev - rho g,
+//          rho = rms(e_c - e_u) / rms(g) * weight per image, no epsilon (ef.py:120-124)
+// V = 4: 128-bit accesses (elems % 4 == 0 and 16-byte aligned bases, checked by the launcher).
+template <int V>
+__global__ __launch_bounds__(256) void step_ef_seed_kernel(const float* __restrict__ g_z, float* __restrict__ d_eps, int n_img,
+                                                           int elems, float w_tar, float c) {
+  const int img = blockIdx.y;
+  const long go = (long)img * elems, uo = go, co = ((long)n_img + img) * elems;
+  const float wu = 1.f - w_tar;
+  for (int i = (blockIdx.x * 256 + threadIdx.x) * V; i < elems; i += gridDim.x * 256 * V) {
+    alignas(16) float g[V], du[V], dc[V];
+    if (V == 4) *reinterpret_cast<float4*>(g) = *reinterpret_cast<const float4*>(g_z + go + i);
+    else g[0] = g_z[go + i];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const float d = c * g[v];
+      du[v] = wu * d;
+      dc[v] = w_tar * d;
+    }
+    if (V == 4) {
+      *reinterpret_cast<float4*>(d_eps + uo + i) = *reinterpret_cast<const float4*>(du);
+      *reinterpret_cast<float4*>(d_eps + co + i) = *reinterpret_cast<const float4*>(dc);
+    } else {
+      d_eps[uo + i] = du[0];
+      d_eps[co + i] = dc[0];
+    }
+  }
+}
+
+// One workgroup per image and a summation order that depends on elems alone: row i of a batch has the bits of a single call.
+// x_out may be x_prev (every element is read and written by the same thread), so neither is __restrict__.
+__global__ __launch_bounds__(1024) void step_ef_style_kernel(const float* __restrict__ e_u, const float* __restrict__ e_c,
+                                                             long stride_img, const float* __restrict__ dx,
+                                                             const float* __restrict__ g_z, const float* x_prev, float* x_out,
+                                                             int n_img, int elems, float a, float weight) {
+  __shared__ float red[16];
+  const int img = blockIdx.x;
+  const long eo = (long)img * stride_img;
+  const float* du = dx + (long)img * elems;
+  const float* dc = dx + ((long)n_img + img) * elems;
+  const float* gi = g_z + (long)img * elems;
+  const float* xp = x_prev + (long)img * elems;
+  float* xo = x_out + (long)img * elems;
+  float sc = 0.f, sg = 0.f;
+  for (int i = threadIdx.x; i < elems; i += blockDim.x) {
+    const float corr = e_c[eo + i] - e_u[eo + i];
+    sc += corr * corr;
+    const float g = (du[i] + dc[i]) + a * gi[i];
+    sg += g * g;
+  }
+  sc = block_sum(sc, red);
+  sg = block_sum(sg, red);
+  const float invn = 1.0f / (float)elems;
+  const float rho = sqrtf(sc * invn) / sqrtf(sg * invn) * weight;
+  for (int i = threadIdx.x; i < elems; i += blockDim.x) {
+    const float g = (du[i] + dc[i]) + a * gi[i];
+    xo[i] = xp[i] - rho * g;
+  }
+}
+
 }  // namespace
+
+int step_ef_seed_launch(const float* g_z, float* d_eps, int n_img, int elems, float w_tar, float c, hipStream_t st) {
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+  const bool vec = elems % 4 == 0 && al16(g_z) && al16(d_eps);
+  const int per = vec ? cdiv(elems, 4) : elems;
+  dim3 grid(cdiv(per, 256) > 64 ? 64 : cdiv(per, 256), n_img);
+  if (vec) hipLaunchKernelGGL(step_ef_seed_kernel<4>, grid, dim3(256), 0, st, g_z, d_eps, n_img, elems, w_tar, c);
+  else hipLaunchKernelGGL(step_ef_seed_kernel<1>, grid, dim3(256), 0, st, g_z, d_eps, n_img, elems, w_tar, c);
+  LAUNCH_CHECK();
+  return HEDIT_OK;
+}
+
+int step_ef_style_launch(const float* e_u, const float* e_c, long stride_img, const float* dx, const float* g_z,
+                         const float* x_prev, float* x_out, int n_img, int elems, float a, float weight, hipStream_t st) {
+  hipLaunchKernelGGL(step_ef_style_kernel, dim3(n_img), dim3(1024), 0, st, e_u, e_c, stride_img, dx, g_z, x_prev, x_out, n_img,
+                     elems, a, weight);
+  LAUNCH_CHECK();
+  return HEDIT_OK;
+}
 
 int step_tweedie_launch(const float* e_u_tar, const float* e_c_tar, long stride_img, const float* x, float* z0,
                         int n_img, int elems, float w_tar, float sqrt_ab, float sqrt_1m_ab, float inv_scale, hipStream_t st) {

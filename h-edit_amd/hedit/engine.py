@@ -117,31 +117,83 @@ class HEditEngine:
         z0 = torch.empty_like(x)
         _lib.check(self.lib.hedit_step_tweedie(_lib.ptr(e_u_tar), _lib.ptr(e_c_tar), elems, _lib.ptr(x), _lib.ptr(z0),
                                                n, elems, float(cfg_scales[2]), sab, s1m, inv_scale, _lib.cur_stream()))
-        shared = not isinstance(image_encoder, (list, tuple))
-        encs = [image_encoder] * n if shared else image_encoder
         g_z = torch.empty_like(x)
-        with torch.enable_grad():
-            # the images are independent: decode a chunk in one pass, one loss per image, and the gradient of
-            # the SUM w.r.t. the chunk's latents is the stack of the per-image gradients
-            for lo in range(0, n, self.style_chunk):
-                hi = min(n, lo + self.style_chunk)
-                zc = z0[lo:hi].clone().requires_grad_(True)
-                img = vae.decode(zc).sample
-                if shared and hasattr(image_encoder, "gram_residual_norms"):
-                    loss = image_encoder.gram_residual_norms(img).sum()          # native on the GPU (csrc/vit.hip)
-                elif (not shared) and all(hasattr(e, "gram_residual_norms_each") for e in encs[lo:hi]):
-                    loss = encs[lo].gram_residual_norms_each(encs[lo:hi], img).sum()     # one call, one reference per image
-                elif shared and hasattr(image_encoder, "gram_residuals"):
-                    loss = torch.linalg.norm(image_encoder.gram_residuals(img), dim=(1, 2)).sum()
-                else:
-                    loss = sum(torch.linalg.norm(encs[i].get_gram_matrix_residual(img[i - lo:i - lo + 1]))
-                               for i in range(lo, hi))
-                g_z[lo:hi] = torch.autograd.grad(outputs=loss, inputs=zc)[0]
+        # the images are independent: decode a chunk in one pass, one loss per image, and the gradient of
+        # the SUM w.r.t. the chunk's latents is the stack of the per-image gradients
+        for lo in range(0, n, self.style_chunk):
+            hi = min(n, lo + self.style_chunk)
+            g_z[lo:hi] = self._gram_grad(z0[lo:hi], image_encoder, lo)
         out = torch.empty_like(x)
         _lib.check(self.lib.hedit_step_style(_lib.ptr(e_u_src), _lib.ptr(e_c_src), _lib.ptr(e_u_tar), _lib.ptr(e_c_tar),
                                              elems, _lib.ptr(x), _lib.ptr(g_z), _lib.ptr(out), n, elems,
                                              float(cfg_scales[1]), float(cfg_scales[2]), inv_scale / sab, float(weight),
                                              _lib.cur_stream()))
+        return out
+
+    def _gram_grad(self, z0, image_encoder, lo):
+        """d(sum of the per-image Gram-residual norms of vae.decode(z0)) / d z0 for the chunk z0 = images lo.. of the batch.
+        ``image_encoder``: one object for all images, or one per image of the BATCH (indexed from lo)."""
+        m = z0.shape[0]
+        shared = not isinstance(image_encoder, (list, tuple))
+        encs = [image_encoder] * m if shared else list(image_encoder[lo:lo + m])
+        with torch.enable_grad():
+            zc = z0.clone().requires_grad_(True)
+            img = self.model.vae.decode(zc).sample
+            if shared and hasattr(image_encoder, "gram_residual_norms"):
+                loss = image_encoder.gram_residual_norms(img).sum()          # native on the GPU (csrc/vit.hip)
+            elif (not shared) and all(hasattr(e, "gram_residual_norms_each") for e in encs):
+                loss = encs[0].gram_residual_norms_each(encs, img).sum()     # one call, one reference per image
+            elif shared and hasattr(image_encoder, "gram_residuals"):
+                loss = torch.linalg.norm(image_encoder.gram_residuals(img), dim=(1, 2)).sum()
+            else:
+                loss = sum(torch.linalg.norm(encs[i].get_gram_matrix_residual(img[i:i + 1])) for i in range(m))
+            return torch.autograd.grad(outputs=loss, inputs=zc)[0]
+
+    def ef_style_step(self, x, x_prev_tar, ctx_uncond, ctx_tar, t, w_tar, image_encoder, weight):
+        """The style step of the Edit Friendly comparison editor (text-guided-n-style/inversion/ef.py:91-124) for n images:
+        x_prev_tar - rho g, g = d ||Gram residual|| / d x THROUGH the eps-network, rho = rms(e_c - e_u) / rms(g) * weight.
+        x (n,C,H,W): the target latents at t; x_prev_tar: their reverse step; ctx_uncond / ctx_tar (n,77,D).  Per chunk of
+        ``style_chunk`` images (one tape lives per UNet handle, so a chunk finishes before the next starts): a kept plain pass
+        [x|uncond, x|tar] -> Tweedie x0 at t (hedit_step_tweedie) -> decoder + image encoder with their gradient, as in
+        style_step -> the cotangent of the pass (hedit_step_ef_seed) -> hedit_unet_backward -> the sum of the gradient's two
+        parts and the update (hedit_step_ef_style).  Nothing here waits for the device (the reference reads two .item())."""
+        unet, vae = self.unet, self.model.vae
+        missing = [w for w, ok in (("model.unet built with its input-gradient pass (UNet2DConditionModel(grad=True))",
+                                    getattr(unet, "grad", False)),
+                                   ("model.vae (hedit.vae.AutoencoderKL)", vae is not None)) if not ok]
+        if missing:
+            raise RuntimeError("ef_style_step needs " + " and ".join(missing))
+        n, elems = x.shape[0], x[0].numel()
+        for t_ in (x, x_prev_tar, ctx_uncond, ctx_tar):
+            assert t_.is_contiguous() and t_.dtype == torch.float32 and t_.shape[0] == n
+        ab = float(self.model.scheduler.alphas_cumprod[int(t)])
+        sab, s1m = ab ** 0.5, (1.0 - ab) ** 0.5
+        inv_scale = 1.0 / 0.18215
+        a = inv_scale / sab
+        c = -a * s1m
+        st = _lib.cur_stream
+        out = torch.empty_like(x_prev_tar)
+        for lo in range(0, n, self.style_chunk):
+            hi = min(n, lo + self.style_chunk)
+            m = hi - lo
+            xc = x[lo:hi]
+            ticket, eps = unet._keep(torch.cat([xc, xc]), float(t), torch.cat([ctx_uncond[lo:hi], ctx_tar[lo:hi]]))
+            e_u, e_c = eps[:m], eps[m:]
+            z0 = torch.empty_like(xc)
+            _lib.check(self.lib.hedit_step_tweedie(_lib.ptr(e_u), _lib.ptr(e_c), elems, _lib.ptr(xc), _lib.ptr(z0), m, elems,
+                                                   float(w_tar), sab, s1m, inv_scale, st()))
+            g_z = self._gram_grad(z0, image_encoder, lo).contiguous()
+            d_eps = torch.empty_like(eps)
+            _lib.check(self.lib.hedit_step_ef_seed(_lib.ptr(g_z), _lib.ptr(d_eps), m, elems, float(w_tar), a, c, st()))
+            if unet._ticket != ticket:
+                raise RuntimeError("hedit.UNet2DConditionModel: the kept forward of this style step was dropped by a later model call")
+            dx = torch.empty_like(eps)
+            with torch.cuda.device(unet.device):
+                _lib.check(self.lib.hedit_unet_backward(unet._h, _lib.ptr(d_eps), _lib.ptr(dx), _lib.ptr(unet._gws), st()))
+            unet._release()
+            _lib.check(self.lib.hedit_step_ef_style(_lib.ptr(e_u), _lib.ptr(e_c), elems, _lib.ptr(dx), _lib.ptr(g_z),
+                                                    _lib.ptr(x_prev_tar[lo:hi]), _lib.ptr(out[lo:hi]), m, elems, a, float(weight),
+                                                    st()))
         return out
 
     # ------------------------------------------------------------------ text

@@ -10,7 +10,12 @@ Differences, all additive:
     ``--random_init`` builds SD-1.x- / ViT-B/16-shaped synthetic weights (``--tiny``: small test sizes).
   * under ``torch.distributed.run`` the dataset entries are sharded across the ranks, one process per
     GPU, no data-path collective (BASELINE configs[4]).
-The ``ef_p2p`` comparison baseline of the reference driver is not part of this build and is refused.
+The ``ef_p2p`` comparison baseline of the reference driver (Edit Friendly, main_edit.py:218-223, inversion/ef.py) runs through
+``edit_ef.py``, which calls ``main`` here with ``modes=("ef_p2p",)``: like the text drivers (main_baselines.py), the h-Edit
+driver itself refuses the comparison modes.  ``ef_p2p`` differentiates the style loss through the eps-network, so it builds the
+UNet with its input-gradient pass (``args.unet_grad``), passes ``cfg_scales = [cfg_src, cfg_tar]`` and takes its weight from
+``--weight_edit_clip_for_ef``.  The output folder keeps the reference's string, which prints ``w_style_{args.weight_edit_clip}``
+(main_edit.py:97) even in that mode: the folder of an ``ef_p2p`` run names the h-Edit weight, not the one it used.
 """
 import argparse
 import os
@@ -24,6 +29,7 @@ if HERE not in sys.path:
 
 from hedit import driver as DR  # noqa: E402
 from hedit.clip_guidance import CLIPEncoder  # noqa: E402
+from hedit.inversion.ef_style import ef_p2p  # noqa: E402
 from hedit.inversion.h_edit import h_Edit_p2p_implicit  # noqa: E402
 from hedit.p2p.ptp_classes import ControllerBatch  # noqa: E402
 from hedit.p2p.ptp_utils import register_attention_control  # noqa: E402
@@ -35,7 +41,7 @@ def build_parser():
     p.add_argument("--device_num", type=int, default=0)
     p.add_argument('--dataset', type=str, default="./assets/demo/")
     p.add_argument('--output_path', type=str, default="./results/demo/")
-    p.add_argument("--mode", default="h_edit_R_p2p", help="modes: h_edit_R_p2p")
+    p.add_argument("--mode", default="h_edit_R_p2p", help="modes: h_edit_R_p2p (ef_p2p: edit_ef.py)")
     p.add_argument("--num_diffusion_steps", type=int, default=50)
     p.add_argument("--skip", type=int, default=0)
     p.add_argument("--eta", type=float, default=1.0)
@@ -78,14 +84,26 @@ def edit_group(args, model, entries, scale, size, device):
     cfg_scales = [args.cfg_src, args.cfg_src_edit, args.cfg_tar]
     w0 = DR.encode_images(model, entries, scale, size, device, "p2p")
     engine = DR.lock_step_engine(model, len(entries))
-    zs, wts, eta = DR.invert(args, model, w0, [p[0] for p in pairs] if engine else pairs[0][0], engine)
+    if args.mode == "ef_p2p" and engine:
+        # image by image, so that the forward process draws the numbers of the one-at-a-time run: the group's results are
+        # then those runs' bit for bit (the inversion is T two-row passes, a small part of this mode's step)
+        inv = [DR.invert(args, model, w0[i:i + 1], p[0]) for i, p in enumerate(pairs)]
+        zs, wts, eta = torch.stack([v[0] for v in inv], 1), torch.stack([v[1] for v in inv], 1), inv[0][2]
+    else:
+        zs, wts, eta = DR.invert(args, model, w0, [p[0] for p in pairs] if engine else pairs[0][0], engine)
     # main_edit.py:185-214: no local blend, no heuristic equaliser for the combined task; the dataset's blended word is
     # re-weighted by 2.0; Replace whenever source and target have the same number of words
     ctrls = [DR.p2p_controller(args, model, item, after_skip_steps, replace=len(p[0].split(" ")) == len(p[1].split(" ")),
                                local_blend=False) for (_, item, _, _), p in zip(entries, pairs)]
     controller = ControllerBatch(ctrls) if engine else ctrls[0]
     register_attention_control(model, controller)
-    if engine:
+    if args.mode == "ef_p2p":                            # main_edit.py:218-223; a group in lock-step, one encoder per image
+        edited, _ = ef_p2p(model, encs if engine else encs[0], xT=wts[after_skip_steps].contiguous(), etas=eta,
+                           prompts=pairs if engine else pairs[0], cfg_scales=[args.cfg_src, args.cfg_tar], prog_bar=True,
+                           zs=zs[:after_skip_steps], controller=controller, weight_edit_clip=args.weight_edit_clip_for_ef,
+                           is_ddim_inversion=False, per_image=True)
+        model.unet.zero_grad()
+    elif engine:
         edited, _ = engine.run(wts[after_skip_steps].contiguous(), zs[:after_skip_steps].contiguous(), pairs, cfg_scales, controller,
                                eta=eta, p2p=True, implicit=True, K=args.optimization_steps, after_skip_steps=after_skip_steps,
                                ddim_inv=False, fuse_src_pass=True, style=(encs, args.weight_edit_clip))
@@ -101,13 +119,16 @@ def edit_group(args, model, entries, scale, size, device):
     return DR.save_group(x0_dec, entries)
 
 
-def main(argv=None):
+def main(argv=None, modes=("h_edit_R_p2p",)):
+    """modes: what this entry runs -- ("h_edit_R_p2p",) for this driver, ("ef_p2p",) from edit_ef.py"""
     args = build_parser().parse_args(argv)
     assert args.eta == 1.0, "eta should be set to 1.0 for this experiment"
     assert args.optimization_steps == 1, "we have not tested multiple optimization steps for this experiment"
     assert args.implicit, "we only demo the implicit form for this experiment"
-    if args.mode != 'h_edit_R_p2p':
-        raise NotImplementedError(f"mode {args.mode}: only h_edit_R_p2p is built")
+    if args.mode not in modes or args.mode not in ("h_edit_R_p2p", "ef_p2p"):
+        raise NotImplementedError(f"mode {args.mode}: this driver runs {', '.join(modes)} (ef_p2p: edit_ef.py)")
+    if args.mode == "ef_p2p":
+        args.unet_grad = True                   # Edit Friendly differentiates through the eps-network
     print(f'Arguments: {args}')
     run = DR.start_run(args, lambda: dataset_from_json(args.dataset + "demo.json"),
                        no_vae="the checkpoint has no vae/ sub-folder: the style closure decodes through it")

@@ -34,6 +34,10 @@
  *   _keep + _backward                 (text-guided-n-style/inversion/h_edit.py:146-185)
  *   hedit_step_tweedie,     replace   reverse_step_pred_x0 and the rho-normalised style update
  *   hedit_step_style                  (inversion_utils.py:128-140, h_edit.py:167-183)
+ *   hedit_step_ef_seed,     replace   the latent-side arithmetic of Edit Friendly's style step, which differentiates the loss
+ *   hedit_step_ef_style               through the eps-network: the cotangent handed to hedit_unet_backward, then the sum of the
+ *                                     gradient's parts and the rho-normalised update with its two .item() syncs
+ *                                     (text-guided-n-style/inversion/ef.py:103-124)
  *   hedit_ddpm_forward      replaces  Model.forward(x, t) of face-swapping/diffusion/diffusion.py:294-341
  *                                     (call sites face-swapping/inversion/h_edit_R.py:71,96,118, sde_inversion.py:121)
  *   hedit_k_*               single-kernel entry points used by the parity tests
@@ -256,6 +260,18 @@ int hedit_step_tweedie(const float* e_u_tar, const float* e_c_tar, int64_t strid
 int hedit_step_style(const float* e_u_src, const float* e_c_src, const float* e_u_tar, const float* e_c_tar,
                      int64_t stride_img, const float* x, const float* g_z, float* x_out, int n_img, int elems,
                      float w_hat, float w_tar, float chain, float weight, void* stream);
+/* Style step of the Edit Friendly comparison editor (text-guided-n-style/inversion/ef.py:91-124).  The loss is differentiated
+ * through a plain UNet pass of 2 n rows [x | uncond] * n, [x | tar] * n (hedit_unet_forward_keep): z0 = hedit_step_tweedie of
+ * its eps with ab at t, g_z = d loss / d z0.  With a = inv_scale / sqrt(ab_t), c = -a sqrt(1 - ab_t):
+ *   step_ef_seed:  d_eps [2 n][elems], the cotangent for hedit_unet_backward: row i = (1 - w_tar) c g_z[i],
+ *                  row n + i = w_tar c g_z[i]   (`a` is not part of it: the direct term is added by step_ef_style)
+ *   step_ef_style: dx [2 n][elems] = what hedit_unet_backward returned; g = (dx[i] + dx[n + i]) + a g_z[i];
+ *                  rho = rms(e_c - e_u) / rms(g) * weight per image, no epsilon (a zero gradient gives the reference's
+ *                  inf / nan); x_out = x_prev - rho g.  x_out may be x_prev.  Row i of a batch has the bits of a single call.
+ * e_u / e_c: pointer to image 0, image i at + i * stride_img; g_z / x_prev / x_out [n_img][elems]. */
+int hedit_step_ef_seed(const float* g_z, float* d_eps, int n_img, int elems, float w_tar, float a, float c, void* stream);
+int hedit_step_ef_style(const float* e_u, const float* e_c, int64_t stride_img, const float* dx, const float* g_z,
+                        const float* x_prev, float* x_out, int n_img, int elems, float a, float weight, void* stream);
 /* A sparse linear map along one axis of a [outer][n_in][inner] fp32 tensor: out[o][i][x] = sum_j val[i][j] in[o][idx[i][j]][x]
  * (tables [n_out][nnz], fixed summation order).  With torch's bicubic weights it replaces F.interpolate(im, (224, 224),
  * mode="bicubic") in front of the style encoder (text-guided-n-style/clip_guidance/base_clip.py:57-58) and, with the
