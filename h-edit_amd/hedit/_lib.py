@@ -67,18 +67,27 @@ class StepCoef(C.Structure):
                                          "noise_coef", "w_src", "w_hat", "w_tar", "coeff", "w_rec")]
 
 
-_SIGS = {
-    "hedit_last_error": (C.c_char_p, []),
+def _family(name, cfg, finalizes, workspace_args):
+    """The entries every network family has: hedit_<name>_create (with its cfg struct, if it has one) / destroy / num_params /
+    param_name / param_shape / load / missing / workspace_bytes(handle, *workspace_args), and finalize where the family packs in a
+    step of its own."""
+    sigs = {"create": (C.c_int, ([C.POINTER(cfg)] if cfg else []) + [C.POINTER(C.c_void_p)]),
+            "destroy": (None, [C.c_void_p]),
+            "num_params": (C.c_int, [C.c_void_p]),
+            "param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
+            "param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+            "load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+            "missing": (C.c_int, [C.c_void_p]),
+            "workspace_bytes": (C.c_size_t, [C.c_void_p] + workspace_args)}
+    if finalizes:
+        sigs["finalize"] = (C.c_int, [C.c_void_p, C.c_void_p])
+    return {f"hedit_{name}_{k}": v for k, v in sigs.items()}
+
+
+_SIGS = {    "hedit_last_error": (C.c_char_p, []),
     "hedit_version": (C.c_int, []),
-    "hedit_unet_create": (C.c_int, [C.POINTER(UnetCfg), C.POINTER(C.c_void_p)]),
-    "hedit_unet_destroy": (None, [C.c_void_p]),
-    "hedit_unet_num_params": (C.c_int, [C.c_void_p]),
-    "hedit_unet_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
-    "hedit_unet_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "hedit_unet_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    **_family("unet", UnetCfg, False, [C.c_int] * 3),
     "hedit_unet_param_bf16_exact": (C.c_int, [C.c_void_p, C.c_int]),
-    "hedit_unet_missing": (C.c_int, [C.c_void_p]),
-    "hedit_unet_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "hedit_unet_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int,
                                      C.c_int, C.POINTER(P2PPlan), C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
@@ -124,14 +133,7 @@ _SIGS = {
                                     C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "hedit_local_blend_sub": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
-    "hedit_ddpm_create": (C.c_int, [C.POINTER(DdpmCfg), C.POINTER(C.c_void_p)]),
-    "hedit_ddpm_destroy": (None, [C.c_void_p]),
-    "hedit_ddpm_num_params": (C.c_int, [C.c_void_p]),
-    "hedit_ddpm_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
-    "hedit_ddpm_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "hedit_ddpm_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_ddpm_missing": (C.c_int, [C.c_void_p]),
-    "hedit_ddpm_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    **_family("ddpm", DdpmCfg, False, [C.c_int]),
     "hedit_ddpm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
     "hedit_ddpm_create_grad": (C.c_int, [C.POINTER(DdpmCfg), C.POINTER(C.c_void_p)]),
@@ -142,112 +144,41 @@ _SIGS = {
     "hedit_ddpm_release": (None, [C.c_void_p]),
     "hedit_ddpm_vjp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_size_t, C.c_void_p]),
-    "hedit_irse50_create": (C.c_int, [C.POINTER(C.c_void_p)]),
-    "hedit_irse50_destroy": (None, [C.c_void_p]),
-    "hedit_irse50_num_params": (C.c_int, [C.c_void_p]),
-    "hedit_irse50_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
-    "hedit_irse50_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "hedit_irse50_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_irse50_missing": (C.c_int, [C.c_void_p]),
-    "hedit_irse50_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "hedit_irse50_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    **_family("irse50", None, True, [C.c_int]),
     "hedit_irse50_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hedit_irse50_cos_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_lpips_create": (C.c_int, [C.POINTER(C.c_void_p)]),
-    "hedit_lpips_destroy": (None, [C.c_void_p]),
-    "hedit_lpips_num_params": (C.c_int, [C.c_void_p]),
-    "hedit_lpips_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
-    "hedit_lpips_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "hedit_lpips_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_lpips_missing": (C.c_int, [C.c_void_p]),
-    "hedit_lpips_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
+    **_family("lpips", None, True, [C.c_int] * 3),
     "hedit_lpips_feature_floats": (C.c_size_t, [C.c_int, C.c_int]),
-    "hedit_lpips_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "hedit_lpips_source": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),
     "hedit_lpips_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_faceparse_create": (C.c_int, [C.POINTER(C.c_void_p)]),
-    "hedit_faceparse_destroy": (None, [C.c_void_p]),
-    "hedit_faceparse_num_params": (C.c_int, [C.c_void_p]),
-    "hedit_faceparse_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
-    "hedit_faceparse_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "hedit_faceparse_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_faceparse_missing": (C.c_int, [C.c_void_p]),
-    "hedit_faceparse_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "hedit_faceparse_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    **_family("faceparse", None, True, [C.c_int] * 3),
     "hedit_faceparse_labels": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_size_t, C.c_void_p]),
     "hedit_face_mask_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hedit_face_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_vit_create": (C.c_int, [C.POINTER(VitCfg), C.POINTER(C.c_void_p)]),
-    "hedit_vit_destroy": (None, [C.c_void_p]),
-    "hedit_vit_num_params": (C.c_int, [C.c_void_p]),
-    "hedit_vit_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
-    "hedit_vit_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "hedit_vit_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_vit_missing": (C.c_int, [C.c_void_p]),
-    "hedit_vit_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "hedit_vit_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
+    **_family("vit", VitCfg, True, [C.c_int]),
     "hedit_vit_gram": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hedit_vit_gram_fwd_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_text_create": (C.c_int, [C.POINTER(TextCfg), C.POINTER(C.c_void_p)]),
-    "hedit_text_destroy": (None, [C.c_void_p]),
-    "hedit_text_num_params": (C.c_int, [C.c_void_p]),
-    "hedit_text_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
-    "hedit_text_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "hedit_text_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_text_missing": (C.c_int, [C.c_void_p]),
-    "hedit_text_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "hedit_text_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    **_family("text", TextCfg, True, [C.c_int] * 2),
     "hedit_text_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                     C.c_size_t, C.c_void_p]),
-    "hedit_clipimg_create": (C.c_int, [C.POINTER(ClipImgCfg), C.POINTER(C.c_void_p)]),
-    "hedit_clipimg_destroy": (None, [C.c_void_p]),
-    "hedit_clipimg_num_params": (C.c_int, [C.c_void_p]),
-    "hedit_clipimg_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
-    "hedit_clipimg_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "hedit_clipimg_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_clipimg_missing": (C.c_int, [C.c_void_p]),
-    "hedit_clipimg_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
+    **_family("clipimg", ClipImgCfg, True, [C.c_int]),
     "hedit_clipimg_set_slices": (C.c_int, [C.c_void_p, C.c_int]),
-    "hedit_clipimg_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int]),
     "hedit_clipimg_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_sqlpips_create": (C.c_int, [C.POINTER(C.c_void_p)]),
-    "hedit_sqlpips_destroy": (None, [C.c_void_p]),
-    "hedit_sqlpips_num_params": (C.c_int, [C.c_void_p]),
-    "hedit_sqlpips_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
-    "hedit_sqlpips_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "hedit_sqlpips_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_sqlpips_missing": (C.c_int, [C.c_void_p]),
-    "hedit_sqlpips_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
-    "hedit_sqlpips_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    **_family("sqlpips", None, True, [C.c_int] * 3),
     "hedit_sqlpips_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_size_t, C.c_void_p]),
-    "hedit_dino_create": (C.c_int, [C.POINTER(DinoCfg), C.POINTER(C.c_void_p)]),
-    "hedit_dino_destroy": (None, [C.c_void_p]),
-    "hedit_dino_num_params": (C.c_int, [C.c_void_p]),
-    "hedit_dino_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
-    "hedit_dino_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "hedit_dino_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_dino_missing": (C.c_int, [C.c_void_p]),
-    "hedit_dino_finalize": (C.c_int, [C.c_void_p, C.c_void_p]),
+    **_family("dino", DinoCfg, True, [C.c_int] * 2),
     "hedit_dino_set_slices": (C.c_int, [C.c_void_p, C.c_int]),
-    "hedit_dino_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
     "hedit_dino_keys": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hedit_dino_structure_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                                 C.c_void_p]),
-    "hedit_vae_create": (C.c_int, [C.POINTER(VaeCfg), C.POINTER(C.c_void_p)]),
-    "hedit_vae_destroy": (None, [C.c_void_p]),
-    "hedit_vae_num_params": (C.c_int, [C.c_void_p]),
-    "hedit_vae_param_name": (C.c_char_p, [C.c_void_p, C.c_int]),
-    "hedit_vae_param_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
-    "hedit_vae_load": (C.c_int, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "hedit_vae_missing": (C.c_int, [C.c_void_p]),
-    "hedit_vae_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    **_family("vae", VaeCfg, False, [C.c_int] * 4),
     "hedit_vae_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_size_t, C.c_void_p]),
     "hedit_vae_decode_vjp": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -21,6 +21,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..native import NativeOwner
+
 # IR-50 layout (helpers.py:37-44): (in_channel, depth, units) per stage, first unit of a stage has stride 2
 _STAGES_50 = ((64, 64, 3), (64, 128, 4), (128, 256, 14), (256, 512, 3))
 
@@ -120,15 +122,14 @@ class _NativeCosSim(torch.autograd.Function):
         return -grad * g.view(-1, 1, 1, 1), None
 
 
-class IDLoss(nn.Module):
+class IDLoss(nn.Module, NativeOwner):
     """``IDLoss(ref_path)`` as the reference, plus where the backbone weights come from: ``weights`` = local
     path of model_ir_se50.pth or a state_dict; None = seeded random weights (synthetic runs).  Every method takes CUDA
     tensors and runs on the HIP executor; there is no CPU / torch path."""
+    _family = "irse50"
 
     def __init__(self, ref_path=None, weights=None, ref=None, device=None, seed=0):
         super().__init__()
-        self._h = None
-        self._ws = None
         self.facenet = Backbone(input_size=112, num_layers=50, drop_ratio=0.6, mode="ir_se")
         if weights is None:
             self.facenet.init_random(seed)
@@ -153,38 +154,13 @@ class IDLoss(nn.Module):
             raise RuntimeError("IDLoss runs on the HIP executor only: pass CUDA tensors (there is no CPU / torch path)")
 
     def _native(self, device):
-        """create / load / finalize the native backbone on first use (parameters by the reference's names)"""
-        import ctypes as C
-        from .. import _lib
-        if self._h is not None:
-            return self._h
-        lib = _lib.lib()
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(lib.hedit_irse50_create(C.byref(h)))
-            sd = self.facenet.state_dict()
-            for i in range(lib.hedit_irse50_num_params(h)):
-                name = lib.hedit_irse50_param_name(h, i).decode()
-                w = sd[name].detach().to(device=device, dtype=torch.float32).contiguous()
-                _lib.check(lib.hedit_irse50_load(h, name.encode(), _lib.ptr(w), w.numel(), _lib.cur_stream()))
-                torch.cuda.current_stream().synchronize()
-            _lib.check(lib.hedit_irse50_finalize(h, _lib.cur_stream()))
-        self._h, self._lib = h, lib
-        return h
-
-    def __del__(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                self._lib.hedit_irse50_destroy(self._h)
-            except Exception:
-                pass
+        """the native backbone on ``device``, built from the parameters (by the reference's names) on first use there"""
+        if self._h is None or self._h_device != device:
+            self._native_build(device, self.facenet.state_dict())
+        return self._h
 
     def _workspace(self, B, device):
-        B = max(B, self.ref.shape[0])
-        need = self._lib.hedit_irse50_workspace_bytes(self._h, B)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return self._ws
+        return self._grow("_ws", self._lib.hedit_irse50_workspace_bytes(self._h, max(B, self.ref.shape[0])), device)
 
     def _to256(self, x):
         """the reference's ``F.adaptive_avg_pool2d(x, (256, 256))`` for inputs of another size (arcface_model.py:41-42).  When

@@ -12,10 +12,10 @@ batch it is called with, and it is always called with ONE image.  ``training=Tru
 therefore uses each image's own (mean, biased variance) over H x W: a batch of B images gives exactly the labels of B
 separate calls.  This deliberately differs from torch at B > 1, which would pool the statistics over the batch.
 ``.eval()`` switches to the running statistics."""
-import ctypes as C
-
 import torch
 import torch.nn as nn
+
+from ..native import NativeOwner
 
 _FILTERS = (64, 128, 256, 512, 1024)
 
@@ -38,12 +38,14 @@ class _UnetUp(nn.Module):
         self.up = nn.ConvTranspose2d(cin, cout, kernel_size=2, stride=2)
 
 
-class FaceParsing(nn.Module):
+class FaceParsing(nn.Module, NativeOwner):
     """``FaceParsing()`` of the reference with its default configuration (the only one built).  ``forward(x)``: fp32
     (B, 3, H, W) in [-1, 1] on the GPU, H and W multiples of 16 -> int64 labels (B, 1, H, W) in [0, n_classes).
 
     The native network is built from the parameters on the first call; ``load_state_dict`` and ``init_random`` drop it,
     other in-place changes of the parameters need ``reset_native()``."""
+    _family = "faceparse"
+    reset_native = NativeOwner._native_release
 
     def __init__(self, feature_scale=4, n_classes=19, is_deconv=True, in_channels=3, is_batchnorm=True, device=None):
         super().__init__()
@@ -69,8 +71,6 @@ class FaceParsing(nn.Module):
         self.final = nn.Conv2d(f[0], n_classes, 1)
         for p in self.parameters():
             p.requires_grad_(False)
-        self._h = None
-        self._ws = None
         if device is not None:
             self.to(device)
 
@@ -110,39 +110,10 @@ class FaceParsing(nn.Module):
         return super().load_state_dict(sd, strict=strict)
 
     # ------------------------------------------------------------------ native executor (csrc/faceparse.hip)
-    def reset_native(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                self._lib.hedit_faceparse_destroy(self._h)
-            except Exception:
-                pass
-        self._h = None
-
-    def __del__(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                self._lib.hedit_faceparse_destroy(self._h)
-            except Exception:
-                pass
-
     def _native(self, device):
-        from .. import _lib
-        if self._h is not None and self._h_device == device:
-            return self._h
-        self.reset_native()
-        lib = _lib.lib()
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(lib.hedit_faceparse_create(C.byref(h)))
-            self._h, self._lib, self._h_device = h, lib, device
-            sd = self.state_dict()
-            for i in range(lib.hedit_faceparse_num_params(h)):
-                name = lib.hedit_faceparse_param_name(h, i).decode()
-                w = sd[name].detach().to(device=device, dtype=torch.float32).contiguous()
-                _lib.check(lib.hedit_faceparse_load(h, name.encode(), _lib.ptr(w), w.numel(), _lib.cur_stream()))
-                torch.cuda.current_stream().synchronize()
-            _lib.check(lib.hedit_faceparse_finalize(h, _lib.cur_stream()))
-        return h
+        if self._h is None or self._h_device != device:
+            self._native_build(device, self.state_dict())
+        return self._h
 
     @staticmethod
     def _check_shape(x):
@@ -164,8 +135,7 @@ class FaceParsing(nn.Module):
         need = self._lib.hedit_faceparse_workspace_bytes(h, B, H, W)
         if need == 0:
             _lib.check(-1)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != x.device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=x.device)
+        self._grow("_ws", need, x.device)
         labels = torch.empty(B, 1, H, W, dtype=torch.int64, device=x.device)
         with torch.cuda.device(x.device):
             _lib.check(self._lib.hedit_faceparse_labels(h, _lib.ptr(x), B, H, W, int(self.training), _lib.ptr(labels),

@@ -14,10 +14,10 @@ wrapped in an autograd node so that the loop's ``torch.autograd.grad(lpips_loss,
 (inversion/h_edit_R.py:124-132) works unchanged.  ``LPIPSNet`` is a PARAMETER CONTAINER (no forward): there is no
 torch / CPU execution path in the product -- the fp32 restatement the native path is tested against lives in
 oracle/reward_nets.py (test infrastructure)."""
-import ctypes as C
-
 import torch
 import torch.nn as nn
+
+from ..native import NativeOwner
 
 _VGG = ((3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256),
         (256, 512), (512, 512), (512, 512), (512, 512), (512, 512), (512, 512))
@@ -80,10 +80,11 @@ class _NativeLpips(torch.autograd.Function):
         return grad * g, None
 
 
-class LPIPS_Loss(nn.Module):
+class LPIPS_Loss(nn.Module, NativeOwner):
     """``LPIPS_Loss(src_path)`` as the reference; plus ``src`` (tensor in [-1, 1], (1,3,H,W) or one source per image
     (n,3,H,W) for lock-step batches), ``weights`` (local path of a saved lpips state_dict, or a dict; None = seeded
     random weights for synthetic runs).  CUDA tensors only: the HIP executor is the one execution path."""
+    _family = "lpips"
 
     def __init__(self, src_path=None, src=None, weights=None, device=None, seed=0):
         super().__init__()
@@ -103,43 +104,18 @@ class LPIPS_Loss(nn.Module):
             from .arcface_model import load_face_image
             src = load_face_image(src_path)
         self.register_buffer("src", src.float())
-        self._h = None
-        self._ws = None
         self._src_feats = None
         if device is not None:
             self.to(device)
 
     # ------------------------------------------------------------------ native executor (csrc/lpips.hip)
     def _native(self, device):
-        from .. import _lib
-        if self._h is not None:
-            return self._h
-        lib = _lib.lib()
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(lib.hedit_lpips_create(C.byref(h)))
-            sd = self.lpips_loss.state_dict()
-            for i in range(lib.hedit_lpips_num_params(h)):
-                name = lib.hedit_lpips_param_name(h, i).decode()
-                w = sd[name].detach().to(device=device, dtype=torch.float32).contiguous()
-                _lib.check(lib.hedit_lpips_load(h, name.encode(), _lib.ptr(w), w.numel(), _lib.cur_stream()))
-                torch.cuda.current_stream().synchronize()
-            _lib.check(lib.hedit_lpips_finalize(h, _lib.cur_stream()))
-        self._h, self._lib = h, lib
-        return h
-
-    def __del__(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                self._lib.hedit_lpips_destroy(self._h)
-            except Exception:
-                pass
+        if self._h is None or self._h_device != device:
+            self._native_build(device, self.lpips_loss.state_dict())
+        return self._h
 
     def _workspace(self, B, H, W, device):
-        need = self._lib.hedit_lpips_workspace_bytes(self._h, B, H, W)
-        if self._ws is None or self._ws.numel() < need or self._ws.device != device:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return self._ws
+        return self._grow("_ws", self._lib.hedit_lpips_workspace_bytes(self._h, B, H, W), device)
 
     def _source_features(self, device, H, W):
         from .. import _lib

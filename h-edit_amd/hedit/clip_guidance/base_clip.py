@@ -21,6 +21,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ..native import NativeOwner
+
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 VIT_B16 = dict(width=768, layers=3, heads=12, patch_size=16, input_resolution=224)
@@ -211,16 +213,15 @@ class _NativeGramResidual(torch.autograd.Function):
         return grad * torch.where(live, nrm, torch.zeros_like(nrm)).view(-1, 1, 1, 1), None
 
 
-class CLIPEncoder(nn.Module):
+class CLIPEncoder(nn.Module, NativeOwner):
     """Reference signature ``CLIPEncoder(need_ref=False, ref_path=None)`` plus where the weights come
     from (the reference downloads them; this build is offline): ``clip_path`` = local checkpoint,
     or ``clip_model`` = a ready ClipVisualPrefix, else seeded random weights (synthetic runs)."""
+    _family = "vit"
 
     def __init__(self, need_ref=False, ref_path=None, clip_path=None, clip_model=None, device=None,
                  dtype=torch.float16, seed=0):
         super().__init__()
-        self._h = None
-        self._ws = None
         self._gram_ref_native = None
         if clip_model is None:
             if clip_path is not None:
@@ -261,38 +262,17 @@ class CLIPEncoder(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("CLIPEncoder runs on the HIP executor only: pass CUDA tensors (there is no CPU / torch path)")
 
-    def _native(self, device):
-        import ctypes as C
-        from .. import _lib
-        if self._h is not None:
-            return self._h
-        lib = _lib.lib()
-        v = self.clip_model.visual
-        cfg = _lib.VitCfg()
-        cfg.width = v.conv1.weight.shape[0]
-        cfg.layers = len(v.transformer.resblocks)
-        cfg.heads = v.transformer.resblocks[0].heads
-        cfg.patch_size = v.conv1.kernel_size[0]
-        cfg.input_resolution = self.size
-        h = C.c_void_p()
-        with torch.cuda.device(device):
-            _lib.check(lib.hedit_vit_create(C.byref(cfg), C.byref(h)))
-            sd = self.clip_model.state_dict()
-            for i in range(lib.hedit_vit_num_params(h)):
-                name = lib.hedit_vit_param_name(h, i).decode()
-                w = sd[name].detach().to(device=device, dtype=torch.float32).contiguous()
-                _lib.check(lib.hedit_vit_load(h, name.encode(), _lib.ptr(w), w.numel(), _lib.cur_stream()))
-                torch.cuda.current_stream().synchronize()
-            _lib.check(lib.hedit_vit_finalize(h, _lib.cur_stream()))
-        self._h, self._lib, self._width = h, lib, cfg.width
-        return h
+    @property
+    def _width(self):
+        return self.clip_model.visual.conv1.weight.shape[0]
 
-    def __del__(self):
-        if getattr(self, "_h", None) is not None and getattr(self, "_owns_handle", True):
-            try:
-                self._lib.hedit_vit_destroy(self._h)
-            except Exception:
-                pass
+    def _native(self, device):
+        from .. import _lib
+        if self._h is None or self._h_device != device:
+            v = self.clip_model.visual
+            cfg = _lib.VitCfg(self._width, len(v.transformer.resblocks), v.transformer.resblocks[0].heads, v.conv1.kernel_size[0], self.size)
+            self._native_build(device, self.clip_model.state_dict(), cfg)
+        return self._h
 
     def sibling(self, ref):
         """Another style reference on the SAME weights: shares this encoder's parameter container, native handle and
@@ -303,11 +283,10 @@ class CLIPEncoder(nn.Module):
         dev = self._mean.device
         if dev.type == "cuda":
             self._native(dev)
-        sib = CLIPEncoder(clip_model=self.clip_model)
+        sib = _Sibling(clip_model=self.clip_model)
+        sib._parent = self
         sib.to(dev)
         sib.set_reference(ref.to(dev))
-        if self._h is not None:
-            sib._h, sib._lib, sib._width, sib._owns_handle, sib._parent = self._h, self._lib, self._width, False, self
         return sib
 
     @staticmethod
@@ -324,11 +303,7 @@ class CLIPEncoder(nn.Module):
         return _NativeGramNorm.apply(x, first, refs)
 
     def _workspace(self, B, device):
-        o = getattr(self, "_parent", None) or self          # siblings use their parent's workspace
-        need = self._lib.hedit_vit_workspace_bytes(self._h, B)
-        if o._ws is None or o._ws.numel() < need or o._ws.device != device:
-            o._ws = torch.empty(need, dtype=torch.uint8, device=device)
-        return o._ws
+        return self._grow("_ws", self._lib.hedit_vit_workspace_bytes(self._h, B), device)
 
     def __deepcopy__(self, memo):
         """a copy owns its own parameters and (lazily) its own native handle -- never a second reference to this one's"""
@@ -393,6 +368,22 @@ class CLIPEncoder(nn.Module):
         self._require_gpu(ims)
         x = self.preprocess(_BicubicResize.apply(ims, self.size))
         return _NativeGramResidual.apply(x, self)
+
+
+class _Sibling(CLIPEncoder):
+    """What ``CLIPEncoder.sibling`` returns: a style reference of its own; the handle, the library and the workspace are
+    the parent's, read at each use, so a parent that rebuilds (another device) takes its siblings with it"""
+    _h = property(lambda self: self._parent._h)
+    _lib = property(lambda self: self._parent._lib)
+
+    def _native(self, device):
+        return self._parent._native(device)
+
+    def _workspace(self, B, device):
+        return self._parent._workspace(B, device)
+
+    def _native_release(self):
+        pass
 
 
 def load_style_reference(path, size=224):

@@ -12,6 +12,7 @@ import os
 import numpy as np
 import torch
 
+from .native import NativeOwner
 from .text import NativeClipText, _cfg_get
 
 CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
@@ -104,11 +105,12 @@ def preprocess_pil(img, size):
     return (x - mean) / std
 
 
-class NativeClipImage:
+class NativeClipImage(NativeOwner):
     """The CLIP image tower on the native executor: a parameter container under the OpenAI CLIP names plus the native
     handle.  There is no torch forward.  ``model(pixel_values)`` -> (B, embed_dim) fp32, not normalised; results are
     bit-identical whatever the batch (``batch_invariant``)."""
     batch_invariant = True
+    _family = "clipimg"
 
     def __init__(self, width, layers, heads, patch_size, input_resolution, embed_dim, device="cuda:0"):
         if width % heads or width // heads != 64:
@@ -126,9 +128,6 @@ class NativeClipImage:
         self.param_shapes = clipimg_param_shapes(self.width, self.layers, self.patch_size, self.input_resolution, self.embed_dim)
         self.params = None
         self.calls = 0                # native encode calls made (tests count them)
-        self._h = None
-        self._lib = None
-        self._ws = None
         self._need = {}
         self._slices = 0
 
@@ -143,7 +142,7 @@ class NativeClipImage:
             if tuple(sd[k].shape) != shape:
                 raise ValueError(f"{k}: expected shape {shape}, got {tuple(sd[k].shape)}")
         self.params = {k: sd[k].detach() for k in self.param_shapes}
-        self._release()
+        self._native_release()
         return self
 
     def state_dict(self):
@@ -207,20 +206,9 @@ class NativeClipImage:
         return self.load_state_dict(sd)
 
     # ------------------------------------------------------------------ the native handle
-    def _release(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                self._lib.hedit_clipimg_destroy(self._h)
-            except Exception:
-                pass
-        self._h = None
-
-    def __del__(self):
-        self._release()
-
     def to(self, device):
         if torch.device(device) != self.device:
-            self._release()
+            self._native_release()
             self.device, self._ws = torch.device(device), None
         return self
 
@@ -237,7 +225,6 @@ class NativeClipImage:
         return self
 
     def _native(self):
-        import ctypes as C
         from . import _lib
         if self._h is not None:
             return self._h
@@ -245,24 +232,9 @@ class NativeClipImage:
             raise RuntimeError("NativeClipImage has no parameters: use one of the from_* loaders or load_state_dict")
         if self.device.type != "cuda":
             raise RuntimeError("NativeClipImage runs on the HIP executor only (there is no CPU / torch path)")
-        lib = _lib.lib()
         cfg = _lib.ClipImgCfg(self.width, self.layers, self.heads, self.patch_size, self.input_resolution, self.embed_dim)
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(lib.hedit_clipimg_create(C.byref(cfg), C.byref(h)))
-            try:
-                for i in range(lib.hedit_clipimg_num_params(h)):
-                    name = lib.hedit_clipimg_param_name(h, i).decode()
-                    w = self.params[name].to(device=self.device, dtype=torch.float32).contiguous()
-                    _lib.check(lib.hedit_clipimg_load(h, name.encode(), _lib.ptr(w), w.numel(), _lib.cur_stream()))
-                    torch.cuda.current_stream().synchronize()
-                _lib.check(lib.hedit_clipimg_finalize(h, _lib.cur_stream()))
-                _lib.check(lib.hedit_clipimg_set_slices(h, self._slices))
-            except Exception:
-                lib.hedit_clipimg_destroy(h)
-                raise
-        self._h, self._lib = h, lib
-        return h
+        return self._native_build(self.device, self.params, cfg,
+                                  after=lambda lib, h: _lib.check(lib.hedit_clipimg_set_slices(h, self._slices)))
 
     def __call__(self, pixel_values):
         from . import _lib
@@ -282,8 +254,7 @@ class NativeClipImage:
                 need = self._need[B] = self._lib.hedit_clipimg_workspace_bytes(h, B)
             if need == 0:
                 _lib.check(self._lib.hedit_clipimg_encode(h, _lib.ptr(x), B, _lib.ptr(out), None, 0, _lib.cur_stream()))   # raises with the library's message
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            self._grow("_ws", need, dev)
             _lib.check(self._lib.hedit_clipimg_encode(h, _lib.ptr(x), B, _lib.ptr(out), _lib.ptr(self._ws), self._ws.numel(), _lib.cur_stream()))
         self.calls += 1
         return out

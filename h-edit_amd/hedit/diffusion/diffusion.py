@@ -9,11 +9,10 @@ state_dict key names of the reference class.  GPU only -- there is no eager path
 mode is on and ``x.requires_grad`` the call is an autograd node whose backward is the executor's input-gradient pass
 (what the face task's Edit Friendly mode differentiates, face-swapping/inversion/ef.py:64-66,95,106).  Weights and ``t``
 take no gradient."""
-import ctypes as C
-
 import torch
 
 from .. import _lib
+from ..native import NativeOwner
 from ..unet import random_state_dict
 
 # the CelebA-HQ 256 x 256 model the reference loads (face-swapping/main_edit.py: config of the DDPM checkpoint)
@@ -49,7 +48,8 @@ class _EpsGrad(torch.autograd.Function):
         return dx, None, None
 
 
-class Model:
+class Model(NativeOwner):
+    _family, _finalizes = "ddpm", False
     # the timestep is a launch parameter: a (n,) tensor that still lives on the host is read without a device
     # synchronisation, so callers that know t on the host (the loops do) should not move it to the GPU first
     accepts_host_timesteps = True
@@ -69,7 +69,6 @@ class Model:
         self.in_channels = cfg["in_channels"]
         self.resolution = cfg["image_size"]
         self.ch = cfg["ch"]
-        self._lib = _lib.lib()
         c = _lib.DdpmCfg()
         c.in_channels, c.out_ch, c.ch = cfg["in_channels"], cfg["out_ch"], cfg["ch"]
         mult = list(cfg["ch_mult"])
@@ -81,49 +80,14 @@ class Model:
             if i != len(mult) - 1:
                 res //= 2
         c.num_res_blocks, c.image_size = cfg["num_res_blocks"], cfg["image_size"]
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            create = self._lib.hedit_ddpm_create_grad if grad else self._lib.hedit_ddpm_create
-            _lib.check(create(C.byref(c), C.byref(h)))
-        self._h = h
+        self._native_build(self.device, None, c, create="create_grad" if grad else "create")
         self.grad = bool(grad)
         self._ticket = 0          # identifies the kept forward; 0 = none
-        self.param_shapes = {}
-        nd, dims = C.c_int(), (C.c_int * 4)()
-        for i in range(self._lib.hedit_ddpm_num_params(self._h)):
-            name = self._lib.hedit_ddpm_param_name(self._h, i).decode()
-            _lib.check(self._lib.hedit_ddpm_param_shape(self._h, i, C.byref(nd), dims))
-            self.param_shapes[name] = tuple(dims[k] for k in range(nd.value))
-        self._ws = None
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.hedit_ddpm_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
+        self.param_shapes = self._native_param_shapes()
 
     # ---------------------------------------------------------------- weights
     def load_state_dict(self, sd, strict=True):
-        sd = {k: v for k, v in sd.items() if k != "logvar"}
-        missing = [k for k in self.param_shapes if k not in sd]
-        extra = [k for k in sd if k not in self.param_shapes]
-        if strict and (missing or extra):
-            raise KeyError(f"state_dict mismatch: missing {missing[:5]} ({len(missing)}), "
-                           f"unexpected {extra[:5]} ({len(extra)})")
-        st = _lib.cur_stream()
-        with torch.cuda.device(self.device):
-            for name, shape in self.param_shapes.items():
-                if name not in sd:
-                    continue
-                w = sd[name]
-                if tuple(w.shape) != shape:
-                    raise ValueError(f"{name}: expected shape {shape}, got {tuple(w.shape)}")
-                w = w.detach().to(device=self.device, dtype=torch.float32).contiguous()
-                _lib.check(self._lib.hedit_ddpm_load(self._h, name.encode(), _lib.ptr(w), w.numel(), st))
-                torch.cuda.current_stream().synchronize()
-        return self
+        return self._native_load({k: v for k, v in sd.items() if k != "logvar"}, strict)
 
     def init_random(self, seed=0):
         sd = random_state_dict(self.param_shapes, seed)
@@ -167,9 +131,7 @@ class Model:
     def _workspace(self, need, what):
         if need == 0:
             raise RuntimeError(what + " failed: " + self._lib.hedit_last_error().decode())
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._grow("_ws", need, self.device)
 
     def _release(self):
         if self._ticket:

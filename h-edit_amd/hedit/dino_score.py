@@ -17,12 +17,13 @@ Nothing is ever fetched and ``torch.hub`` is never called: weights come from a l
 and there is no torch forward -- ``DinoNet`` is a parameter container, CPU tensors raise.  Square images only; a checkpoint
 whose ``pos_embed`` does not fit the resolution is refused (positional-embedding interpolation is out of scope).
 """
-import ctypes as C
 import os
 import re
 
 import numpy as np
 import torch
+
+from .native import NativeOwner
 
 MAX_PAIRS = 64            # HEDIT_DINO_MAX_PAIRS of include/hedit.h
 MAX_TOKENS = 1025         # the executor's cap (csrc/dino.hip LMAX)
@@ -170,11 +171,12 @@ def preprocess_pair(img_pred, img_gt, mask_pred=None, mask_gt=None):
     return torch.from_numpy(np.ascontiguousarray(np.transpose(a, (2, 0, 1)))), torch.from_numpy(np.ascontiguousarray(np.transpose(b, (2, 0, 1))))
 
 
-class NativeDinoStructure:
+class NativeDinoStructure(NativeOwner):
     """``weights``: None (seeded stand-in weights of the configuration in ``standin``, synthetic runs), a ``DinoNet``, a state
     dict, or a LOCAL path (``read_weights``).  ``distance`` is bit-identical whatever the batch (``batch_invariant``),
     symmetric in its two arguments, and exactly 0 for equal images."""
     batch_invariant = True
+    _family = "dino"
 
     def __init__(self, weights=None, device="cuda:0", seed=0, resolution=224, key_layer=11, **standin):
         if weights is None:
@@ -185,54 +187,22 @@ class NativeDinoStructure:
             self.net = DinoNet.from_state_dict(weights if isinstance(weights, dict) else read_weights(weights), resolution, key_layer)
         self.device = torch.device(device)
         self.calls = 0                # native distance calls made (tests count them)
-        self._h = None
-        self._lib = None
-        self._ws = None
 
     # ------------------------------------------------------------------ the native handle
-    def _release(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                self._lib.hedit_dino_destroy(self._h)
-            except Exception:
-                pass
-        self._h = None
-
-    def __del__(self):
-        self._release()
-
     def _native(self):
         from . import _lib
         if self._h is not None:
             return self._h
         if self.device.type != "cuda":
             raise RuntimeError("NativeDinoStructure runs on the HIP executor only (there is no CPU path)")
-        lib = _lib.lib()
         n = self.net
-        cfg = _lib.DinoCfg(n.width, n.layers, n.heads, n.patch, n.resolution, n.key_layer)
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(lib.hedit_dino_create(C.byref(cfg), C.byref(h)))
-            try:
-                for i in range(lib.hedit_dino_num_params(h)):
-                    name = lib.hedit_dino_param_name(h, i).decode()
-                    w = n.params[name].to(device=self.device, dtype=torch.float32).contiguous()
-                    _lib.check(lib.hedit_dino_load(h, name.encode(), _lib.ptr(w), w.numel(), _lib.cur_stream()))
-                    torch.cuda.current_stream().synchronize()
-                _lib.check(lib.hedit_dino_finalize(h, _lib.cur_stream()))
-            except Exception:
-                lib.hedit_dino_destroy(h)
-                raise
-        self._h, self._lib = h, lib
-        return h
+        return self._native_build(self.device, n.params, _lib.DinoCfg(n.width, n.layers, n.heads, n.patch, n.resolution, n.key_layer))
 
     def _workspace(self, pairs, S):
         need = self._lib.hedit_dino_workspace_bytes(self._h, pairs, S)
         if need == 0:
             raise ValueError(f"structure distance: {pairs} pair(s) of side {S} are outside what the executor runs")
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._grow("_ws", need, self.device)
 
     def _check(self, t, what):
         if not torch.is_tensor(t) or not t.is_cuda:

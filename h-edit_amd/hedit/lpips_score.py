@@ -12,12 +12,13 @@ executor against a torch restatement of this description (tests/helpers/sqlpips_
 Nothing is ever fetched: weights come from local files or from seeded stand-in values, and there is no torch forward --
 ``SqueezeLpipsNet`` is a parameter container, CPU tensors raise.
 """
-import ctypes as C
 import os
 import re
 
 import numpy as np
 import torch
+
+from .native import NativeOwner
 
 # torchvision features index, input channels, squeeze channels, channels of each expand (csrc/sqlpips.hip FIRE)
 FIRES = ((3, 64, 16, 64), (4, 128, 16, 64), (6, 128, 32, 128), (7, 256, 32, 128),
@@ -156,11 +157,12 @@ def preprocess_pair(img_pred, img_gt, mask_pred=None, mask_gt=None):
     return (torch.tensor(a).permute(2, 0, 1) * 2 - 1).contiguous(), (torch.tensor(b).permute(2, 0, 1) * 2 - 1).contiguous()
 
 
-class NativeSqueezeLpips:
+class NativeSqueezeLpips(NativeOwner):
     """``weights``: None (seeded stand-in weights, synthetic runs), a local path, a state dict, or a pair (backbone, lins)
     of those -- see ``read_weights``.  ``distance`` is bit-identical whatever the batch (``batch_invariant``), symmetric in
     its two arguments, and exactly 0 for equal images."""
     batch_invariant = True
+    _family = "sqlpips"
 
     def __init__(self, weights=None, device="cuda:0", seed=0):
         self.net = SqueezeLpipsNet()
@@ -170,44 +172,14 @@ class NativeSqueezeLpips:
             self.net.load_state_dict(read_weights(weights))
         self.device = torch.device(device)
         self.calls = 0                # native distance calls made (tests count them)
-        self._h = None
-        self._lib = None
-        self._ws = None
 
     # ------------------------------------------------------------------ the native handle
-    def _release(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                self._lib.hedit_sqlpips_destroy(self._h)
-            except Exception:
-                pass
-        self._h = None
-
-    def __del__(self):
-        self._release()
-
     def _native(self):
-        from . import _lib
         if self._h is not None:
             return self._h
         if self.device.type != "cuda":
             raise RuntimeError("NativeSqueezeLpips runs on the HIP executor only (there is no CPU / torch path)")
-        lib = _lib.lib()
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(lib.hedit_sqlpips_create(C.byref(h)))
-            try:
-                for i in range(lib.hedit_sqlpips_num_params(h)):
-                    name = lib.hedit_sqlpips_param_name(h, i).decode()
-                    w = self.net.params[name].to(device=self.device, dtype=torch.float32).contiguous()
-                    _lib.check(lib.hedit_sqlpips_load(h, name.encode(), _lib.ptr(w), w.numel(), _lib.cur_stream()))
-                    torch.cuda.current_stream().synchronize()
-                _lib.check(lib.hedit_sqlpips_finalize(h, _lib.cur_stream()))
-            except Exception:
-                lib.hedit_sqlpips_destroy(h)
-                raise
-        self._h, self._lib = h, lib
-        return h
+        return self._native_build(self.device, self.net.params)
 
     # ------------------------------------------------------------------ the metric
     def distance(self, a, b):
@@ -230,8 +202,7 @@ class NativeSqueezeLpips:
         out = torch.empty(N, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
             need = self._lib.hedit_sqlpips_workspace_bytes(h, N, H, W)
-            if self._ws is None or self._ws.numel() < max(need, 1):
-                self._ws = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+            self._grow("_ws", max(need, 1), dev)
             _lib.check(self._lib.hedit_sqlpips_distance(h, _lib.ptr(a), _lib.ptr(b), N, H, W, _lib.ptr(out), _lib.ptr(self._ws), self._ws.numel(),
                                                         _lib.cur_stream()))
         self.calls += 1

@@ -12,6 +12,8 @@ import types
 import torch
 import torch.nn as nn
 
+from .native import NativeOwner
+
 
 class WordTokenizer:
     """Whitespace word-level tokenizer with the CLIPTokenizer surface used by the path
@@ -243,7 +245,7 @@ class TextEncoderOutput:
         return 2
 
 
-class NativeClipText:
+class NativeClipText(NativeOwner):
     """The CLIP text transformer on the native executor (``hedit_text_*`` of libhedit_hip.so, csrc/text.hip): a parameter
     container under the OpenAI CLIP names plus the native handle.  There is no torch forward.  ``model.text_encoder(ids)[0]``
     works as with transformers' CLIPTextModel; results are bit-identical whatever the batch (``batch_invariant``), so
@@ -253,6 +255,7 @@ class NativeClipText:
     config carries the legacy ``eos_token_id = 2`` as SD-1.x checkpoints do) unless another ``eos_token_id`` is given,
     then the first occurrence of it (transformers' modeling_clip.py)."""
     batch_invariant = True
+    _family = "text"
 
     def __init__(self, width, layers, heads, vocab_size, context_length, proj_dim=0, eos_token_id=None, device="cuda:0"):
         if width % heads or width // heads != 64:
@@ -266,9 +269,6 @@ class NativeClipText:
         self.param_shapes = text_param_shapes(self.width, self.layers, self.vocab_size, self.context_length, self.proj_dim)
         self.params = None
         self.calls = 0                # native encode calls made (tests count them)
-        self._h = None
-        self._lib = None
-        self._ws = None
         self._need = {}               # workspace bytes per (B, L): the query is a dry run of the whole forward
 
     # ------------------------------------------------------------------ parameters
@@ -282,7 +282,7 @@ class NativeClipText:
             if tuple(sd[k].shape) != shape:
                 raise ValueError(f"{k}: expected shape {shape}, got {tuple(sd[k].shape)}")
         self.params = {k: sd[k].detach() for k in self.param_shapes}
-        self._release()
+        self._native_release()
         return self
 
     def state_dict(self):
@@ -336,20 +336,9 @@ class NativeClipText:
             standin_to_clip_names(enc))
 
     # ------------------------------------------------------------------ the native handle
-    def _release(self):
-        if getattr(self, "_h", None) is not None:
-            try:
-                self._lib.hedit_text_destroy(self._h)
-            except Exception:
-                pass
-        self._h = None
-
-    def __del__(self):
-        self._release()
-
     def to(self, device):
         if torch.device(device) != self.device:
-            self._release()
+            self._native_release()
             self.device, self._ws = torch.device(device), None
         return self
 
@@ -357,7 +346,6 @@ class NativeClipText:
         return self
 
     def _native(self):
-        import ctypes as C
         from . import _lib
         if self._h is not None:
             return self._h
@@ -365,23 +353,8 @@ class NativeClipText:
             raise RuntimeError("NativeClipText has no parameters: use one of the from_* loaders or load_state_dict")
         if self.device.type != "cuda":
             raise RuntimeError("NativeClipText runs on the HIP executor only (there is no CPU / torch path)")
-        lib = _lib.lib()
         cfg = _lib.TextCfg(self.width, self.layers, self.heads, self.vocab_size, self.context_length, self.proj_dim)
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(lib.hedit_text_create(C.byref(cfg), C.byref(h)))
-            try:
-                for i in range(lib.hedit_text_num_params(h)):
-                    name = lib.hedit_text_param_name(h, i).decode()
-                    w = self.params[name].to(device=self.device, dtype=torch.float32).contiguous()
-                    _lib.check(lib.hedit_text_load(h, name.encode(), _lib.ptr(w), w.numel(), _lib.cur_stream()))
-                    torch.cuda.current_stream().synchronize()
-                _lib.check(lib.hedit_text_finalize(h, _lib.cur_stream()))
-            except Exception:
-                lib.hedit_text_destroy(h)
-                raise
-        self._h, self._lib = h, lib
-        return h
+        return self._native_build(self.device, self.params, cfg)
 
     def pool_index(self, input_ids):
         if self.eos_token_id is None:
@@ -412,8 +385,7 @@ class NativeClipText:
             if need == 0:
                 _lib.check(self._lib.hedit_text_encode(h, _lib.ptr(ids), B, L, _lib.ptr(hidden), _lib.ptr(pidx), _lib.ptr(pooled), None, 0,
                                                        _lib.cur_stream()))          # raises with the library's message
-            if self._ws is None or self._ws.numel() < need:
-                self._ws = torch.empty(need, dtype=torch.uint8, device=dev)
+            self._grow("_ws", need, dev)
             _lib.check(self._lib.hedit_text_encode(h, _lib.ptr(ids), B, L, _lib.ptr(hidden), _lib.ptr(pidx), _lib.ptr(pooled),
                                                    _lib.ptr(self._ws), self._ws.numel(), _lib.cur_stream()))
         self.calls += 1

@@ -32,6 +32,7 @@ import math
 import torch
 
 from . import _lib
+from .native import NativeOwner
 
 SD15_CONFIG = dict(in_channels=4, out_channels=4, sample_size=64,
                    block_out_channels=(320, 640, 1280, 1280),
@@ -117,7 +118,8 @@ class _EpsGrad(torch.autograd.Function):
         return dx, dc, None, None
 
 
-class UNet2DConditionModel:
+class UNet2DConditionModel(NativeOwner):
+    _family, _finalizes = "unet", False
     _tickets = 0      # kept forwards so far, over all models: a ticket is never reused
 
     def __init__(self, config=None, device="cuda:0", grad=False):
@@ -129,7 +131,6 @@ class UNet2DConditionModel:
             raise RuntimeError("hedit.UNet2DConditionModel runs on the GPU only (HIP kernels)")
         self.in_channels = cfg["in_channels"]
         self.sample_size = cfg["sample_size"]
-        self._lib = _lib.lib()
         c = _lib.UnetCfg()
         c.in_channels, c.out_channels, c.sample_size = cfg["in_channels"], cfg["out_channels"], cfg["sample_size"]
         ch = list(cfg["block_out_channels"])
@@ -143,59 +144,21 @@ class UNet2DConditionModel:
         c.heads = cfg["attention_head_dim"]
         c.norm_num_groups = cfg["norm_num_groups"]
         self._cfg_struct = c
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            if isinstance(grad, str) and grad != "context":
-                raise ValueError(f'grad must be False, True or "context", got {grad!r}')
-            create = (self._lib.hedit_unet_create_grad_ctx if grad == "context" else
-                      self._lib.hedit_unet_create_grad if grad else self._lib.hedit_unet_create)
-            _lib.check(create(C.byref(c), C.byref(h)))
-        self._h = h
+        if isinstance(grad, str) and grad != "context":
+            raise ValueError(f'grad must be False, True or "context", got {grad!r}')
+        self._native_build(self.device, None, c, create="create_grad_ctx" if grad == "context" else "create_grad" if grad else "create")
         self.grad = bool(grad)
         self.grad_context = grad == "context"      # the handle also differentiates encoder_hidden_states
         self._ticket = 0          # identifies the kept forward; 0 = none
         self._gws = None          # the tape's workspace (hedit_unet_grad_workspace_bytes)
-        self.param_shapes = {}
-        self.bf16_exact = set()       # parameters the executor keeps as unscaled bf16 copies (hedit.dist sends those as bf16)
-        nd, dims = C.c_int(), (C.c_int * 4)()
-        for i in range(self._lib.hedit_unet_num_params(self._h)):
-            name = self._lib.hedit_unet_param_name(self._h, i).decode()
-            _lib.check(self._lib.hedit_unet_param_shape(self._h, i, C.byref(nd), dims))
-            self.param_shapes[name] = tuple(dims[k] for k in range(nd.value))
-            if self._lib.hedit_unet_param_bf16_exact(self._h, i):
-                self.bf16_exact.add(name)
+        self.param_shapes = self._native_param_shapes()
+        # parameters the executor keeps as unscaled bf16 copies (hedit.dist sends those as bf16)
+        self.bf16_exact = {name for i, name in enumerate(self.param_shapes) if self._lib.hedit_unet_param_bf16_exact(self._h, i)}
         self._procs = {n: AttnProcessor() for n in self._processor_names()}
-        self._ws = None
         self.heads = cfg["attention_head_dim"]
 
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.hedit_unet_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
-
     # ---------------------------------------------------------------- weights
-    def load_state_dict(self, sd, strict=True):
-        missing = [k for k in self.param_shapes if k not in sd]
-        extra = [k for k in sd if k not in self.param_shapes]
-        if strict and (missing or extra):
-            raise KeyError(f"state_dict mismatch: missing {missing[:5]} ({len(missing)}), "
-                           f"unexpected {extra[:5]} ({len(extra)})")
-        st = _lib.cur_stream()
-        with torch.cuda.device(self.device):
-            for name, shape in self.param_shapes.items():
-                if name not in sd:
-                    continue
-                w = sd[name]
-                if tuple(w.shape) != shape:
-                    raise ValueError(f"{name}: expected shape {shape}, got {tuple(w.shape)}")
-                w = w.detach().to(device=self.device, dtype=torch.float32).contiguous()
-                _lib.check(self._lib.hedit_unet_load(self._h, name.encode(), _lib.ptr(w), w.numel(), st))
-                # the pack kernels are stream-ordered; keep `w` alive until they ran
-                torch.cuda.current_stream().synchronize()
-        return self
+    load_state_dict = NativeOwner._native_load
 
     def init_random(self, seed=0):
         sd = random_state_dict(self.param_shapes, seed)
@@ -270,10 +233,7 @@ class UNet2DConditionModel:
         need = self._lib.hedit_unet_workspace_bytes(self._h, B, H, W)
         if need == 0:
             raise _lib.HipError("workspace planning failed: " + self._lib.hedit_last_error().decode())
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._grow("_ws", need, self.device)
 
     # ---------------------------------------------------------------- sampled launch timing
     PROF_KINDS = ("conv3x3_gemm", "linear_gemm", "self_attn", "cross_attn", "norm", "other")
@@ -360,9 +320,7 @@ class UNet2DConditionModel:
         need = self._lib.hedit_unet_grad_workspace_bytes(self._h, B, H, W)
         if need == 0:
             raise _lib.HipError("gradient workspace planning failed: " + self._lib.hedit_last_error().decode())
-        if self._gws is None or self._gws.numel() < need:
-            self._gws = None
-            self._gws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._grow("_gws", need, self.device)
         eps = torch.empty(B, self.config["out_channels"], H, W, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.hedit_unet_forward_keep(self._h, _lib.ptr(sample), C.c_float(float(t)), _lib.ptr(ctx), B, H, W,

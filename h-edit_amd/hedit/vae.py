@@ -6,11 +6,10 @@ and ``vae.decode(1 / 0.18215 * latents).sample`` (main_p2p.py:263); ``config.sca
 Weights are addressed by their diffusers state_dict names (the pre-0.18 attention names
 query/key/value/proj_attn are accepted as aliases).  GPU only -- there is no eager path.
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
+from .native import NativeOwner
 from .unet import random_state_dict
 
 SD15_VAE_CONFIG = dict(in_channels=3, latent_channels=4, block_out_channels=(128, 256, 512, 512),
@@ -76,7 +75,9 @@ class _DecodeFn(torch.autograd.Function):
         return vae.decode_vjp(z, d_image), None
 
 
-class AutoencoderKL:
+class AutoencoderKL(NativeOwner):
+    _family, _finalizes = "vae", False
+
     def __init__(self, config=None, device="cuda:0"):
         cfg = dict(SD15_VAE_CONFIG)
         cfg.update(config or {})
@@ -84,7 +85,6 @@ class AutoencoderKL:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("hedit.AutoencoderKL runs on the GPU only (HIP kernels)")
-        self._lib = _lib.lib()
         c = _lib.VaeCfg()
         c.in_channels, c.latent_channels = cfg["in_channels"], cfg["latent_channels"]
         ch = list(cfg["block_out_channels"])
@@ -92,28 +92,11 @@ class AutoencoderKL:
         for i, v in enumerate(ch):
             c.block_out_channels[i] = v
         c.layers_per_block, c.norm_num_groups = cfg["layers_per_block"], cfg["norm_num_groups"]
-        h = C.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.hedit_vae_create(C.byref(c), C.byref(h)))
-        self._h = h
+        self._native_build(self.device, None, c)
         self.factor = 2 ** (len(ch) - 1)
-        self.param_shapes = {}
-        nd, dims = C.c_int(), (C.c_int * 4)()
-        for i in range(self._lib.hedit_vae_num_params(self._h)):
-            name = self._lib.hedit_vae_param_name(self._h, i).decode()
-            _lib.check(self._lib.hedit_vae_param_shape(self._h, i, C.byref(nd), dims))
-            self.param_shapes[name] = tuple(dims[k] for k in range(nd.value))
-        self._ws = None
+        self.param_shapes = self._native_param_shapes()
         self._ws_tape = None          # workspace holding the tape of the last differentiable decode
         self._tape_id, self._tape_live = 0, False
-
-    def __del__(self):
-        try:
-            if getattr(self, "_h", None):
-                self._lib.hedit_vae_destroy(self._h)
-                self._h = None
-        except Exception:
-            pass
 
     # ---------------------------------------------------------------- weights
     @staticmethod
@@ -128,28 +111,14 @@ class AutoencoderKL:
         return ren
 
     def load_state_dict(self, sd, strict=True):
-        sd = self.current_names(sd)
-        missing = [k for k in self.param_shapes if k not in sd]
-        extra = [k for k in sd if k not in self.param_shapes]
-        if strict and (missing or extra):
-            raise KeyError(f"state_dict mismatch: missing {missing[:5]} ({len(missing)}), "
-                           f"unexpected {extra[:5]} ({len(extra)})")
-        st = _lib.cur_stream()
-        with torch.cuda.device(self.device):
-            for name, shape in self.param_shapes.items():
-                if name not in sd:
-                    continue
-                w = sd[name]
-                if w.dim() == 2 and len(shape) == 4:       # pre-0.18 checkpoints store 1x1 convs as linears and vice versa
-                    w = w[:, :, None, None]
-                if w.dim() == 4 and len(shape) == 2:
-                    w = w[:, :, 0, 0]
-                if tuple(w.shape) != shape:
-                    raise ValueError(f"{name}: expected shape {shape}, got {tuple(w.shape)}")
-                w = w.detach().to(device=self.device, dtype=torch.float32).contiguous()
-                _lib.check(self._lib.hedit_vae_load(self._h, name.encode(), _lib.ptr(w), w.numel(), st))
-                torch.cuda.current_stream().synchronize()
-        return self
+        def fit(name, w):
+            shape = self.param_shapes[name]
+            if w.dim() == 2 and len(shape) == 4:       # pre-0.18 checkpoints store 1x1 convs as linears and vice versa
+                w = w[:, :, None, None]
+            if w.dim() == 4 and len(shape) == 2:
+                w = w[:, :, 0, 0]
+            return w
+        return self._native_load(self.current_names(sd), strict, fit)
 
     def init_random(self, seed=0):
         sd = random_state_dict(self.param_shapes, seed)
@@ -161,10 +130,7 @@ class AutoencoderKL:
         need = self._lib.hedit_vae_workspace_bytes(self._h, B, lh, lw, int(encode))
         if need == 0:
             raise RuntimeError("hedit_vae_workspace_bytes failed: " + self._lib.hedit_last_error().decode())
-        if self._ws is None or self._ws.numel() < need:
-            self._ws = None
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return self._grow("_ws", need, self.device)
 
     def decode(self, z, return_dict=True):
         """z (B, latent_channels, h, w) -> .sample (B, in_channels, h*f, w*f), fp32.  Differentiable
@@ -195,10 +161,7 @@ class AutoencoderKL:
         need = self._lib.hedit_vae_workspace_bytes(self._h, B, lh, lw, 2)
         if need == 0:
             raise RuntimeError("hedit_vae_workspace_bytes failed: " + self._lib.hedit_last_error().decode())
-        if self._ws_tape is None or self._ws_tape.numel() < need:
-            self._ws_tape = None
-            self._ws_tape = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ws = self._ws_tape
+        ws = self._grow("_ws_tape", need, self.device)
         img = torch.empty(B, self.config["in_channels"], lh * self.factor, lw * self.factor, dtype=torch.float32,
                           device=self.device)
         with torch.cuda.device(self.device):
