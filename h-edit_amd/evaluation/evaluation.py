@@ -24,6 +24,11 @@ metric needs third-party checkpoints that do not exist offline and is not part o
 row f4 "then the evaluator"): ``local_clip`` (prompt templates + CLIP RN50 / ViT-B/32) -- asking for it, or for a CLIP
 score / LPIPS / structure distance without its model, raises with the name of the missing checkpoint instead of writing a
 made-up number.
+
+``--native_pixel`` (with ``--device cuda``) moves the pixel columns themselves to the native executor (hedit/pixel_score.py,
+csrc/pixmetrics.hip): the same formulas on the uint8 images, fp64 after the fp32 difference, binary masks only.  ``--batch N``
+evaluates up to N (annotation entry, method) pairs of one image size per scorer call -- every native scorer is bit-identical
+whatever the batch, so the CSV is byte for byte the ``--batch 1`` one.
 """
 import argparse
 import csv
@@ -36,6 +41,7 @@ import torch.nn.functional as F
 from PIL import Image
 
 PIXEL_METRICS = ("psnr", "mse", "ssim")
+PIXEL_METRICS_ORDER = ("mse", "psnr", "ssim")        # the columns of a pixel scorer's 3 x 3 result (hedit.pixel_score.METRICS)
 NETWORK_METRICS = {"lpips": "torchmetrics LPIPS (SqueezeNet) weights", "structure_distance": "DINO ViT-B/8 weights (a local state dict: --dino_path)",
                    "clip_similarity_source_image": "CLIP ViT-L/14 weights", "clip_similarity_target_image": "CLIP ViT-L/14 weights",
                    "clip_similarity_target_image_edit_part": "CLIP ViT-L/14 weights", "local_clip": "CLIP ViT-B/32 weights"}
@@ -84,9 +90,10 @@ class MetricsCalculator:
     """The pixel metrics and the CLIP score of the reference's MetricsCalculator (matrics_calculator.py:271-390), same method
     names.  `clip`: a CLIP scorer (hedit.clip_score.NativeClip); without one ``calculate_clip_similarity`` raises.  `lpips`:
     an LPIPS scorer (hedit.lpips_score.NativeSqueezeLpips); without one ``calculate_lpips`` raises.  `dino`: a structure
-    scorer (hedit.dino_score.NativeDinoStructure); without one ``calculate_structure_distance`` raises."""
+    scorer (hedit.dino_score.NativeDinoStructure); without one ``calculate_structure_distance`` raises.  `pixel`: a pixel
+    scorer (hedit.pixel_score.NativePixelMetrics); without one ``calculate_mse`` / ``_psnr`` / ``_ssim`` are the torch code below."""
 
-    def __init__(self, device="cpu", clip=None, lpips=None, dino=None):
+    def __init__(self, device="cpu", clip=None, lpips=None, dino=None, pixel=None):
         self.device = device
         self.clip = clip              # hedit.clip_score.NativeClip (or anything with score(uint8 H x W x 3 array, text)), or None
         self.lpips = lpips            # hedit.lpips_score.NativeSqueezeLpips (or anything with score(pred, gt, mask_pred, mask_gt)), or None
@@ -97,6 +104,9 @@ class MetricsCalculator:
             _require_cuda(device, "LPIPS", "SqueezeNet-LPIPS runs")
         if dino is not None:
             _require_cuda(device, "structure distance", "the DINO key extractor runs")
+        self.pixel = pixel            # hedit.pixel_score.NativePixelMetrics (or anything with score(metric, pred, gt, mask_pred, mask_gt)), or None
+        if pixel is not None:
+            _require_cuda(device, "native pixel metrics", "the pixel-metrics kernel runs")
 
     def calculate_structure_distance(self, img_pred, img_gt, mask_pred=None, mask_gt=None):
         """matrics_calculator.py:390-410: both images as float32 in 0...255 (NOT / 255), times their masks, through the DINO
@@ -126,15 +136,21 @@ class MetricsCalculator:
         return float(self.clip.score(img, txt))
 
     def calculate_mse(self, img_pred, img_gt, mask_pred=None, mask_gt=None):
+        if self.pixel is not None:
+            return float(self.pixel.score("mse", img_pred, img_gt, mask_pred, mask_gt))
         a, b = _pair(img_pred, img_gt, mask_pred, mask_gt)
         return float(((a.to(self.device) - b.to(self.device)) ** 2).mean().item())
 
     def calculate_psnr(self, img_pred, img_gt, mask_pred=None, mask_gt=None):
+        if self.pixel is not None:
+            return float(self.pixel.score("psnr", img_pred, img_gt, mask_pred, mask_gt))
         a, b = _pair(img_pred, img_gt, mask_pred, mask_gt)
         mse = ((a.to(self.device) - b.to(self.device)) ** 2).mean()
         return float((10.0 * torch.log10(1.0 / mse)).item())                 # data_range = 1
 
     def calculate_ssim(self, img_pred, img_gt, mask_pred=None, mask_gt=None):
+        if self.pixel is not None:
+            return float(self.pixel.score("ssim", img_pred, img_gt, mask_pred, mask_gt))
         a, b = _pair(img_pred, img_gt, mask_pred, mask_gt)
         a, b = a.to(self.device), b.to(self.device)
         C = a.shape[1]
@@ -183,6 +199,89 @@ def calculate_metric(mc, metric, src_image, tgt_image, src_mask, tgt_mask, src_p
     return fn(src_image, tgt_image, src_mask, tgt_mask)
 
 
+def _split_metric(metric):
+    """(base, part) as calculate_metric splits a column name; part is None, "_unedit_part" or "_edit_part" """
+    for suffix in ("_unedit_part", "_edit_part"):
+        if metric.endswith(suffix) and not metric.startswith("clip_similarity"):
+            return metric[:-len(suffix)], suffix
+    return metric, None
+
+
+def _grouped_request(mc, metric, it):
+    """What calculate_metric would hand to a scorer for column `metric` of item `it` (a dict with src, tgt, mask, src_p,
+    tgt_p): "nan" where one of its nan rules fires, (family, arguments) for a scorer call, or None for everything that is not
+    a scorer call (the torch pixel path, a refusal): calculate_metric itself then runs for that item."""
+    src, tgt, mask = it["src"], it["tgt"], it["mask"]
+    if metric.startswith("clip_similarity_") and metric in NETWORK_METRICS and getattr(mc, "clip", None) is not None:
+        if metric == "clip_similarity_source_image":
+            return "clip", (np.array(src), it["src_p"])
+        if metric == "clip_similarity_target_image":
+            return "clip", (np.array(tgt), it["tgt_p"])
+        if mask.sum() == 0:
+            return "nan"
+        return "clip", (np.uint8(np.array(tgt) * np.array(mask)), it["tgt_p"])
+    base, part = _split_metric(metric)
+    family = {"lpips": "lpips", "structure_distance": "dino"}.get(base, "pixel" if base in PIXEL_METRICS else None)
+    if family is None or getattr(mc, family, None) is None:
+        return None
+    if part is None:
+        return family, (src, tgt, None, None)
+    if part == "_unedit_part":
+        if (1 - mask).sum() == 0:
+            return "nan"
+        return family, (src, tgt, 1 - mask, 1 - mask)
+    if mask.sum() == 0:
+        return "nan"
+    return family, (src, tgt, mask, mask)
+
+
+def evaluate_group(mc, metrics, items):
+    """Every column of `metrics` for every item of the group (one image size) -> one list of values per item, the values
+    calculate_metric gives item by item.  A scorer with a batched ``scores`` gets one call per column -- the pixel scorer ONE
+    call for all its columns: an item's whole / edit / unedit parts come out of the same native call --, a scorer without one
+    is called item by item.  The nan rules are applied per item before anything reaches a scorer."""
+    values = [[None] * len(metrics) for _ in items]
+    requests = [[_grouped_request(mc, m, it) for m in metrics] for it in items]
+    pixel_rows = {}
+    pixel = getattr(mc, "pixel", None)
+    if pixel is not None and hasattr(pixel, "scores"):
+        live = [i for i, reqs in enumerate(requests) if any(isinstance(r, tuple) and r[0] == "pixel" for r in reqs)]
+        if live:
+            def item(i):
+                masked = any(isinstance(r, tuple) and r[0] == "pixel" and r[1][2] is not None for r in requests[i])
+                it = items[i]
+                return (it["src"], it["tgt"], it["mask"], it["mask"]) if masked else (it["src"], it["tgt"])
+            pixel_rows = dict(zip(live, pixel.scores([item(i) for i in live])))
+    for j, metric in enumerate(metrics):
+        base, part = _split_metric(metric)
+        calls = []
+        for i, it in enumerate(items):
+            r = requests[i][j]
+            if r == "nan":
+                values[i][j] = "nan"
+            elif r is None or (r[0] == "pixel" and i not in pixel_rows):
+                values[i][j] = calculate_metric(mc, metric, it["src"], it["tgt"], it["mask"], it["mask"], it["src_p"], it["tgt_p"])
+            elif r[0] == "pixel":
+                values[i][j] = float(pixel_rows[i][(None, "_edit_part", "_unedit_part").index(part), PIXEL_METRICS_ORDER.index(base)])
+            else:
+                calls.append((i, r))
+        if not calls:
+            continue
+        family = calls[0][1][0]
+        scorer = getattr(mc, family)
+        if family != "clip":
+            for _, (_, a) in calls:
+                assert np.array(a[0]).shape == np.array(a[1]).shape, "Image shapes should be the same."
+        if hasattr(scorer, "scores"):
+            got = scorer.scores([a[0] for _, (_, a) in calls], [a[1] for _, (_, a) in calls]) if family == "clip" else \
+                scorer.scores([a for _, (_, a) in calls])
+        else:
+            got = [scorer.score(*a) for _, (_, a) in calls]
+        for (i, _), v in zip(calls, got):
+            values[i][j] = float(v)
+    return values
+
+
 def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument('--annotation_mapping_file', type=str, default="./PIE_Bench_Data/mapping_file.json")
@@ -206,6 +305,11 @@ def build_parser():
                         "directory holding exactly one .pth")
     p.add_argument('--dino_resolution', type=int, default=224,
                    help="the side the DINO input is resized to; the checkpoint's pos_embed must fit it (no interpolation)")
+    p.add_argument('--native_pixel', action="store_true",
+                   help="compute the psnr* / mse* / ssim* columns with the native pixel-metrics kernel (needs --device cuda; binary masks)")
+    p.add_argument('--batch', type=int, default=1,
+                   help="evaluate up to N (annotation entry, method) pairs of one image size per scorer call; the CSV is byte for byte "
+                        "the --batch 1 one")
     return p
 
 
@@ -235,10 +339,70 @@ def load_dino(dino_path, device, resolution=224):
     return NativeDinoStructure(dino_path, device="cuda:0" if str(device) == "cuda" else device, resolution=resolution)
 
 
-def main(argv=None, clip=None, lpips=None, dino=None):
-    """`clip` / `lpips` / `dino`: ready scorers instead of --clip_path / --lpips_path / --dino_path (synthetic runs and
-    tests: NativeClip.from_standin, NativeSqueezeLpips(), NativeDinoStructure())"""
+def load_pixel(device):
+    """The native pixel-metrics scorer of --native_pixel on `device`"""
+    _require_cuda(device, "--native_pixel", "the pixel-metrics kernel runs")
+    from hedit.pixel_score import NativePixelMetrics
+    return NativePixelMetrics(device="cuda:0" if str(device) == "cuda" else device)
+
+
+def _entries(args, folders, annotation):
+    """(key, source image, mask, source prompt, target prompt, [target image per method]) per selected annotation entry, read
+    exactly as the per-image loop of main reads them"""
+    for key, item in annotation.items():
+        if item["editing_type_id"] not in args.edit_category_list:
+            continue
+        src_image = Image.open(os.path.join(args.src_image_folder, item["image_path"])).convert("RGB")
+        mask = mask_decode(item.get("mask", []), image_shape=(src_image.size[1], src_image.size[0]))
+        mask = mask[:, :, np.newaxis].repeat([3], axis=2)
+        src_p = item["original_prompt"].replace("[", "").replace("]", "")
+        tgt_p = item["editing_prompt"].replace("[", "").replace("]", "")
+        tgts = []
+        for folder in folders.values():
+            tgt = Image.open(os.path.join(folder, item["image_path"])).convert("RGB")
+            if tgt.size[0] != tgt.size[1]:       # result sheets: the edited image is the right-most square (evaluation.py:203-205)
+                s = src_image.size[0]
+                tgt = tgt.crop((tgt.size[0] - s, tgt.size[1] - s, tgt.size[0], tgt.size[1]))
+            tgts.append(tgt)
+        yield key, src_image, mask, src_p, tgt_p, tgts
+
+
+def _run_grouped(args, mc, folders, entries):
+    """--batch N > 1: the (annotation entry, method) pairs in annotation order, in groups of up to N of one image size; a row
+    is written as soon as it and every row before it are complete"""
+    pending, group, written = [], [], 0          # pending: [key, values per (method, metric)] in annotation order
+
+    def flush():
+        nonlocal written
+        if group:
+            for it, vals in zip(group, evaluate_group(mc, args.metrics, group)):
+                it["row"][it["at"]:it["at"] + len(vals)] = vals
+            group.clear()
+        while pending and all(v is not None for v in pending[0]):
+            with open(args.result_path, 'a+', newline="") as f:
+                csv.writer(f).writerow(pending.pop(0))
+            written += 1
+
+    for key, src_image, mask, src_p, tgt_p, tgts in entries:
+        row = [key] + [None] * (len(folders) * len(args.metrics))
+        pending.append(row)
+        for k, tgt in enumerate(tgts):
+            it = dict(src=src_image, tgt=tgt, mask=mask, src_p=src_p, tgt_p=tgt_p, row=row, at=1 + k * len(args.metrics))
+            if group and (group[0]["src"].size, group[0]["tgt"].size) != (src_image.size, tgt.size):
+                flush()
+            group.append(it)
+            if len(group) >= args.batch:
+                flush()
+    flush()
+    return written
+
+
+def main(argv=None, clip=None, lpips=None, dino=None, pixel=None):
+    """`clip` / `lpips` / `dino` / `pixel`: ready scorers instead of --clip_path / --lpips_path / --dino_path / --native_pixel
+    (synthetic runs and tests: NativeClip.from_standin, NativeSqueezeLpips(), NativeDinoStructure(), NativePixelMetrics())"""
     args = build_parser().parse_args(argv)
+    if args.batch < 1:
+        raise SystemExit("--batch N: N >= 1")
     if not args.tgt_folders or len(args.tgt_folders) != len(args.tgt_methods):
         raise SystemExit("give --tgt_folders DIR ... (one per method)")
     folders = dict(zip(args.tgt_methods, args.tgt_folders))
@@ -248,12 +412,18 @@ def main(argv=None, clip=None, lpips=None, dino=None):
         lpips = load_lpips(args.lpips_path, args.device)
     if dino is None and args.dino_path:
         dino = load_dino(args.dino_path, args.device, args.dino_resolution)
-    mc = MetricsCalculator(args.device, clip, lpips, dino)
+    if pixel is None and args.native_pixel:
+        pixel = load_pixel(args.device)
+    mc = MetricsCalculator(args.device, clip, lpips, dino, pixel=pixel)
     os.makedirs(os.path.dirname(os.path.abspath(args.result_path)), exist_ok=True)
     with open(args.result_path, 'w', newline="") as f:
         csv.writer(f).writerow(["file_id"] + [f"{k}|{m}" for k in folders for m in args.metrics])
     with open(args.annotation_mapping_file) as f:
         annotation = json.load(f)
+    if args.batch > 1:
+        rows = _run_grouped(args, mc, folders, _entries(args, folders, annotation))
+        print(f"evaluated {rows} image(s) -> {args.result_path}")
+        return rows
     rows = 0
     for key, item in annotation.items():
         if item["editing_type_id"] not in args.edit_category_list:

@@ -835,6 +835,25 @@ size_t hedit_face_mask_workspace_bytes(int B, int height, int width);
 int hedit_face_mask(const int64_t* labels, int B, int height, int width, int kernel_size, float threshold, int iterations,
                     float* soft, uint8_t* hard, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Pixel metrics of the PIE-Bench evaluator (the psnr*, mse*, ssim* columns): torchmetrics' MeanSquaredError,
+ * PeakSignalNoiseRatio(data_range=1) and StructuralSimilarityIndexMeasure(data_range=1) as
+ * text-guided/evaluation/matrics_calculator.py:272-279 instantiates them, for N pairs and all three parts in one call.
+ * pred, gt: uint8 [N][H][W][3] (what np.array(PIL image) holds); mask_pred, mask_gt: uint8 [N][H][W] with values 0 / 1, either may
+ * be null = all ones.  out: double [N][3][3] = parts (whole, edit, unedit) x (mse, psnr, ssim): whole ignores the masks, edit
+ * multiplies each image by its mask, unedit by 1 - mask; with both masks null the edit and unedit rows are NaN.
+ * a = float(u8) / 255.0f times the mask and d = a - b in fp32; everything after that in fp64: mse = sum d d / (3 H W),
+ * psnr = 10 log10(1 / mse) (+inf for mse 0), ssim = the mean over the (H - 10) x (W - 10) x 3 windows inside the image of the
+ * 11-tap Gaussian (sigma 1.5, the evaluator's fp32 taps, separable) SSIM quotient with c1 = 1e-4, c2 = 9e-4.  Equal images
+ * give exactly 0, +inf and 1.  Two launches, no atomics, fixed reduction order, nothing synchronises; out[n] has the bits of
+ * the N = 1 call on pair n, in either storage build.  HEDIT_ERR_ARG for H or W outside [11, 16384], N outside
+ * [1, HEDIT_PIXEL_METRICS_MAX_BATCH], a null pred / gt / out / workspace, an out or workspace that is not 8-byte aligned, or a
+ * workspace below hedit_pixel_metrics_workspace_bytes(N, H, W) (0 for sizes out of range): all before anything is launched. */
+#define HEDIT_PIXEL_METRICS_MAX_BATCH 64
+size_t hedit_pixel_metrics_workspace_bytes(int N, int height, int width);
+int hedit_pixel_metrics(const uint8_t* pred, const uint8_t* gt, const uint8_t* mask_pred, const uint8_t* mask_gt, int N, int height,
+                        int width, double* out, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
