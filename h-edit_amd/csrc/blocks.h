@@ -1,7 +1,6 @@
-// Blocks shared by the convolutional executors (vae.hip: SD image autoencoder; ddpm.hip: pixel-space
-// DDPM UNet): parameter store addressed by state_dict names, ResNet block (optionally with a timestep-
-// embedding bias), single-head spatial attention done with GEMMs, and their input-gradient passes.
-// Header-only, every includer gets its own copy in an anonymous namespace.
+// Blocks shared by the convolutional executors (vae.hip: SD image autoencoder; ddpm.hip: pixel-space DDPM UNet): ResNet block
+// (optionally with a timestep-embedding bias), single-head spatial attention done with GEMMs, and their input-gradient passes,
+// registered in the parameter store of store.h.  Header-only, every includer gets its own copy in an anonymous namespace.
 #pragma once
 #include <map>
 #include <string>
@@ -11,30 +10,9 @@
 #include "common.h"
 #include "exec.h"
 #include "kernels.h"
-
-#define TRY(expr)                        \
-  do {                                   \
-    int _rc = (expr);                    \
-    if (_rc != HEDIT_OK) return _rc;     \
-  } while (0)
-
+#include "store.h"
 
 namespace {
-
-struct VSlot {
-  std::string name;
-  int kind;        // 0 fp32 copy, 1 linear / 1x1 -> bf16, 2 conv3x3 OIHW -> bf16 [O][9][I]
-  void* dst;
-  size_t numel;
-  int O, I;
-  bool loaded;
-  int ndim;
-  int dims[4];
-  // input-gradient twin (image decoder, pixel UNet with gradient), filled by the same load call:
-  // 0 none, 1 bf16 [I][O], 2 bf16 [I][9][O] taps flipped, 3 fp32 IOHW taps flipped, 4 bf16 [I][9][O] taps in place (stride-2 dgrad)
-  int tkind = 0;
-  void* tdst = nullptr;
-};
 
 struct VRes {
   int cin, cout;
@@ -53,69 +31,6 @@ struct VAttn {
   bf16_t *w_q_t = nullptr, *w_k_t = nullptr, *w_v_t = nullptr, *w_o_t = nullptr;
 };
 
-// parameters of one network, owned device copies; the public handles derive from this
-struct ParamStore {
-  bool alloc_failed = false;
-  std::vector<void*> owned;
-  std::vector<VSlot> slots;
-  std::map<std::string, int> index;
-};
-
-template <class T>
-T* dalloc(ParamStore* h, size_t n) {
-  void* p = nullptr;
-  if (hipMalloc(&p, n * sizeof(T) > 0 ? n * sizeof(T) : 16) != hipSuccess) {
-    h->alloc_failed = true;
-    return nullptr;
-  }
-  h->owned.push_back(p);
-  return reinterpret_cast<T*>(p);
-}
-
-void add_slot(ParamStore* h, const std::string& name, int kind, void* dst, size_t numel, int O, int I, int ndim,
-              int d0, int d1, int d2, int d3) {
-  VSlot s{name, kind, dst, numel, O, I, false, ndim, {d0, d1, d2, d3}};
-  h->index[name] = (int)h->slots.size();
-  h->slots.push_back(s);
-}
-float* vec(ParamStore* h, const std::string& name, int n) {
-  float* d = dalloc<float>(h, n);
-  add_slot(h, name, 0, d, n, 0, 0, 1, n, 1, 1, 1);
-  return d;
-}
-float* mat(ParamStore* h, const std::string& name, int O, int I) {   // a [O][I] matrix kept fp32 (packed by the executor's finalize)
-  float* d = dalloc<float>(h, (size_t)O * I);
-  add_slot(h, name, 0, d, (size_t)O * I, O, I, 2, O, I, 1, 1);
-  return d;
-}
-float* f32conv(ParamStore* h, const std::string& name, int O, int I, int k) {   // kept fp32, torch layout
-  float* d = dalloc<float>(h, (size_t)O * I * k * k);
-  add_slot(h, name, 0, d, (size_t)O * I * k * k, O, I, 4, O, I, k, k);
-  return d;
-}
-bf16_t* lin(ParamStore* h, const std::string& name, int O, int I, bool conv1x1 = false) {
-  bf16_t* d = dalloc<bf16_t>(h, (size_t)O * I);
-  add_slot(h, name, 1, d, (size_t)O * I, O, I, conv1x1 ? 4 : 2, O, I, 1, 1);
-  return d;
-}
-bf16_t* conv3(ParamStore* h, const std::string& name, int O, int I) {
-  // at least 4 rows (zero beyond O): a conv with <= 4 output channels can then run as an N = 4 GEMM
-  const int rows = O < 4 ? 4 : O;
-  bf16_t* d = dalloc<bf16_t>(h, (size_t)rows * I * 9);
-  if (d && rows != O && hipMemset(d, 0, (size_t)rows * I * 9 * sizeof(bf16_t)) != hipSuccess) h->alloc_failed = true;
-  add_slot(h, name, 2, d, (size_t)O * I * 9, O, I, 4, O, I, 3, 3);
-  return d;
-}
-
-// attach an input-gradient twin to the slot just added
-template <class T>
-T* twin(ParamStore* h, int tkind, size_t n) {
-  T* d = dalloc<T>(h, n);
-  h->slots.back().tkind = tkind;
-  h->slots.back().tdst = d;
-  return d;
-}
-
 // Parameter naming of the two families: diffusers (AutoencoderKL) and the DDPM code base of the face model
 struct BlockNames {
   const char* shortcut;                 // 1x1 shortcut conv of a ResNet block
@@ -133,7 +48,7 @@ VRes make_res(ParamStore* h, const std::string& pre, int cin, int cout, bool gra
   r.n1g = vec(h, pre + ".norm1.weight", cin);
   r.n1b = vec(h, pre + ".norm1.bias", cin);
   r.conv1 = conv3(h, pre + ".conv1.weight", cout, cin);
-  if (grad) r.conv1_t = twin<bf16_t>(h, 2, (size_t)cout * cin * 9);
+  if (grad) r.conv1_t = twin<bf16_t>(h, Pack::Conv3Dgrad, (size_t)cout * cin * 9);
   r.c1b = vec(h, pre + ".conv1.bias", cout);
   if (temb_ch > 0) {
     r.temb_ch = temb_ch;
@@ -143,11 +58,11 @@ VRes make_res(ParamStore* h, const std::string& pre, int cin, int cout, bool gra
   r.n2g = vec(h, pre + ".norm2.weight", cout);
   r.n2b = vec(h, pre + ".norm2.bias", cout);
   r.conv2 = conv3(h, pre + ".conv2.weight", cout, cout);
-  if (grad) r.conv2_t = twin<bf16_t>(h, 2, (size_t)cout * cout * 9);
+  if (grad) r.conv2_t = twin<bf16_t>(h, Pack::Conv3Dgrad, (size_t)cout * cout * 9);
   r.c2b = vec(h, pre + ".conv2.bias", cout);
   if (cin != cout) {
     r.sc_w = lin(h, pre + nm.shortcut + ".weight", cout, cin, true);
-    if (grad) r.sc_t = twin<bf16_t>(h, 1, (size_t)cout * cin);
+    if (grad) r.sc_t = twin<bf16_t>(h, Pack::LinearT, (size_t)cout * cin);
     r.sc_b = vec(h, pre + nm.shortcut + ".bias", cout);
   }
   return r;
@@ -160,16 +75,16 @@ VAttn make_attn(ParamStore* h, const std::string& pre, int C, bool grad = false,
   a.gn_g = vec(h, pre + nm.a_norm + ".weight", C);
   a.gn_b = vec(h, pre + nm.a_norm + ".bias", C);
   a.w_q = lin(h, pre + nm.a_q + ".weight", C, C, c4);
-  if (grad) a.w_q_t = twin<bf16_t>(h, 1, (size_t)C * C);
+  if (grad) a.w_q_t = twin<bf16_t>(h, Pack::LinearT, (size_t)C * C);
   a.q_b = vec(h, pre + nm.a_q + ".bias", C);
   a.w_k = lin(h, pre + nm.a_k + ".weight", C, C, c4);
-  if (grad) a.w_k_t = twin<bf16_t>(h, 1, (size_t)C * C);
+  if (grad) a.w_k_t = twin<bf16_t>(h, Pack::LinearT, (size_t)C * C);
   a.k_b = vec(h, pre + nm.a_k + ".bias", C);      // loaded for completeness; softmax-invariant (see vae.hip header)
   a.w_v = lin(h, pre + nm.a_v + ".weight", C, C, c4);
-  if (grad) a.w_v_t = twin<bf16_t>(h, 1, (size_t)C * C);
+  if (grad) a.w_v_t = twin<bf16_t>(h, Pack::LinearT, (size_t)C * C);
   a.v_b = vec(h, pre + nm.a_v + ".bias", C);
   a.w_o = lin(h, pre + nm.a_o + ".weight", C, C, c4);
-  if (grad) a.w_o_t = twin<bf16_t>(h, 1, (size_t)C * C);
+  if (grad) a.w_o_t = twin<bf16_t>(h, Pack::LinearT, (size_t)C * C);
   a.o_b = vec(h, pre + nm.a_o + ".bias", C);
   return a;
 }
@@ -194,21 +109,6 @@ struct GnStat {
 // statistics' summation order, like every other one here, must not depend on what shares the launch
 inline bool gn_stats_shape(const VF& f, int HW, int C) {
   return f.gn_fuse && HW >= 1024 && HW % 128 == 0 && C % 128 == 0 && gemm_pick_bn(C) == 128;
-}
-
-#define RUN(f, expr)            \
-  do {                          \
-    if (!(f).dry()) TRY(expr);  \
-  } while (0)
-
-template <class T>
-int aalloc(VF& f, T** out, size_t n) {
-  *out = reinterpret_cast<T*>(f.ar.alloc(n * sizeof(T)));
-  if (!*out) {
-    hedit_set_error("workspace too small (need more than " + std::to_string(f.ar.cap) + " bytes)");
-    return HEDIT_ERR_ARG;
-  }
-  return HEDIT_OK;
 }
 
 // batch_in: which extent carries the batch (1 = M, 2 = N, 0 = neither); the K-chunking comes from the per-image
@@ -550,59 +450,6 @@ int attention_bwd(VF& f, const AttnRec& rec, const bf16_t* dy, bf16_t** dx_out) 
   f.ar.free(dxn);
   *dx_out = dx;
   return HEDIT_OK;
-}
-
-// ---- generic parameter access behind the C ABI of every executor
-inline int store_load(ParamStore* h, const char* what, const char* name, const float* w, size_t numel, hipStream_t st) {
-  auto it = h->index.find(name);
-  if (it == h->index.end()) {
-    hedit_set_error(std::string("unknown ") + what + " parameter: " + name);
-    return HEDIT_ERR_ARG;
-  }
-  VSlot& s = h->slots[it->second];
-  if (s.numel != numel) {
-    hedit_set_error(std::string("size mismatch for ") + name + ": expected " + std::to_string(s.numel) + ", got " + std::to_string(numel));
-    return HEDIT_ERR_ARG;
-  }
-  if (s.kind == 0) {
-    HIP_TRY(hipMemcpyAsync(s.dst, w, numel * sizeof(float), hipMemcpyDeviceToDevice, st));
-  } else if (s.kind == 1) {
-    TRY(pack_linear_launch(w, reinterpret_cast<bf16_t*>(s.dst), (long)numel, 1.0f, st));
-  } else {
-    TRY(pack_conv3x3_launch(w, reinterpret_cast<bf16_t*>(s.dst), s.O, s.I, st));
-  }
-  if (s.tkind == 1) {
-    TRY(pack_linear_t_launch(w, reinterpret_cast<bf16_t*>(s.tdst), s.O, s.I, st));
-  } else if (s.tkind == 2) {
-    TRY(pack_conv3x3_dgrad_launch(w, reinterpret_cast<bf16_t*>(s.tdst), s.O, s.I, st));
-  } else if (s.tkind == 3) {
-    TRY(flip_oihw_launch(w, reinterpret_cast<float*>(s.tdst), s.O, s.I, s.dims[2], st));
-  } else if (s.tkind == 4) {
-    TRY(pack_conv3x3_s2_dgrad_launch(w, reinterpret_cast<bf16_t*>(s.tdst), s.O, s.I, st));
-  }
-  s.loaded = true;
-  return HEDIT_OK;
-}
-inline int store_missing(const ParamStore* h) {
-  int m = 0;
-  for (auto& s : h->slots) m += s.loaded ? 0 : 1;
-  return m;
-}
-// the parameter table as the *_num_params / *_param_name / *_param_shape entries of every handle report it
-inline int store_num_params(const ParamStore* h) { return h ? (int)h->slots.size() : 0; }
-inline const char* store_param_name(const ParamStore* h, int i) {
-  if (!h || i < 0 || i >= (int)h->slots.size()) return nullptr;
-  return h->slots[i].name.c_str();
-}
-inline int store_param_shape(const ParamStore* h, int i, int* ndim, int* dims4) {
-  ARG_CHECK(h && ndim && dims4 && i >= 0 && i < (int)h->slots.size(), "param index");
-  *ndim = h->slots[i].ndim;
-  for (int k = 0; k < 4; ++k) dims4[k] = h->slots[i].dims[k];
-  return HEDIT_OK;
-}
-inline void store_free(ParamStore* h) {
-  for (void* p : h->owned) if (p) (void)hipFree(p);
-  h->owned.clear();
 }
 
 }  // namespace

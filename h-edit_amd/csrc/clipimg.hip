@@ -148,7 +148,7 @@ __global__ __launch_bounds__(256, 2) void tiled_attn_kernel(const float* __restr
 
 }  // namespace
 
-struct hedit_clipimg : ParamStore {
+struct HEDIT_HANDLE hedit_clipimg : ParamStore {
   hedit_clipimg_cfg cfg;
   int L = 0, P = 0;
   int slices = 0;                 // > 0: the attention grid's slice count (hedit_clipimg_set_slices), else one per pass
@@ -156,7 +156,6 @@ struct hedit_clipimg : ParamStore {
         *proj_w = nullptr;
   PConv conv, proj;
   std::vector<EncBlock> blocks;
-  bool finalized = false;
 };
 
 namespace {
@@ -169,14 +168,14 @@ int run(hedit_clipimg* h, const float* img, int B, float* out, void* ws, size_t 
   const long Mp = (long)B * (L - 1), M = (long)B * L;
   const float ascale = 1.0f / sqrtf((float)HD);
   float *X0, *Em, *T0, *T;
-  TRY(palloc(f, &X0, (size_t)Mp * K0));
+  TRY(aalloc(f, &X0, (size_t)Mp * K0));
   if (!dry) TRY(enc_patchify_launch(img, X0, B, R, p, 0, st));
   TRY(lin(f, X0, K0, P_COPY, nullptr, nullptr, h->conv, false, Mp, &Em));
   f.ar.free(X0);
-  TRY(palloc(f, &T0, (size_t)M * W));
+  TRY(aalloc(f, &T0, (size_t)M * W));
   if (!dry) TRY(enc_tokens_launch(Em, nullptr, h->cls, h->pos, T0, B, L, W, st));
   f.ar.free(Em);
-  TRY(palloc(f, &T, (size_t)M * W));
+  TRY(aalloc(f, &T, (size_t)M * W));
   TRY(ln(f, T0, h->lnpg, h->lnpb, M, W, LN_EPS, T));
   f.ar.free(T0);
   auto attn = [&](const float* qkv, const float* bias, float* A) -> int {
@@ -187,9 +186,9 @@ int run(hedit_clipimg* h, const float* img, int B, float* out, void* ws, size_t 
   for (const EncBlock& k : h->blocks) TRY(enc_block_forward(f, k, T, M, W, P_QGELU, LN_EPS, attn));
   // ln_post on the class row, times visual.proj: text.hip's pooled path with row 0
   float *Rw, *N, *o;
-  TRY(palloc(f, &Rw, (size_t)B * W));
+  TRY(aalloc(f, &Rw, (size_t)B * W));
   if (!dry) TRY(enc_gather_rows_launch(T, nullptr, Rw, B, L, W, st));
-  TRY(palloc(f, &N, (size_t)B * W));
+  TRY(aalloc(f, &N, (size_t)B * W));
   TRY(ln(f, Rw, h->lnog, h->lnob, B, W, LN_EPS, N));
   TRY(lin(f, N, W, P_COPY, nullptr, nullptr, h->proj, true, B, &o));            // one M = B GEMM: x @ visual.proj
   if (!dry) HIP_TRY(hipMemcpyAsync(out, o, (size_t)B * E * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -202,6 +201,8 @@ int run(hedit_clipimg* h, const float* img, int B, float* out, void* ws, size_t 
 }
 
 }  // namespace
+
+HEDIT_LIFECYCLE(clipimg, hedit_clipimg, "CLIP image tower", no_pre_destroy)
 
 extern "C" {
 
@@ -230,38 +231,12 @@ int hedit_clipimg_create(const hedit_clipimg_cfg* cfg, hedit_clipimg** out) try 
   h->lnog = vec(h, "visual.ln_post.weight", W);
   h->lnob = vec(h, "visual.ln_post.bias", W);
   h->proj_w = mat(h, "visual.proj", W, E);
-  if (h->alloc_failed) {
-    hedit_set_error("hipMalloc failed while creating the CLIP image tower");
-    store_free(h);
-    delete h;
-    return HEDIT_ERR_HIP;
-  }
-  *out = h;
-  return HEDIT_OK;
+  return handle_created(h, out);
 } catch (...) { return hedit_abi_catch(); }
-
-void hedit_clipimg_destroy(hedit_clipimg* h) try {
-  if (!h) return;
-  store_free(h);
-  delete h;
-} catch (...) { (void)hedit_abi_catch(); }
-
-int hedit_clipimg_num_params(const hedit_clipimg* h) { return store_num_params(h); }
-const char* hedit_clipimg_param_name(const hedit_clipimg* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_clipimg_param_shape(const hedit_clipimg* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
-int hedit_clipimg_load(hedit_clipimg* h, const char* name, const float* w, size_t numel, void* stream) try {
-  ARG_CHECK(h && name && w, "null");
-  h->finalized = false;
-  return store_load(h, "CLIP image tower", name, w, numel, reinterpret_cast<hipStream_t>(stream));
-} catch (...) { return hedit_abi_catch(); }
-int hedit_clipimg_missing(const hedit_clipimg* h) { return h ? store_missing(h) : -1; }
 
 int hedit_clipimg_finalize(hedit_clipimg* h, void* stream) try {
   ARG_CHECK(h, "null");
-  if (store_missing(h) != 0) {
-    hedit_set_error("CLIP image tower has " + std::to_string(store_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(handle_loaded(h));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int W = h->cfg.width, p = h->cfg.patch_size;
   // conv1 weight [W][3][p][p] flattened = a linear map over (c, ky, kx)
@@ -286,8 +261,8 @@ int hedit_clipimg_set_slices(hedit_clipimg* h, int slices) try {
 size_t hedit_clipimg_workspace_bytes(hedit_clipimg* h, int B) try {
   if (!h || B < 1 || B > HEDIT_CLIPIMG_MAX_BATCH) return 0;
   size_t peak = 0;
-  if (run(h, nullptr, B, reinterpret_cast<float*>(4096), nullptr, 0, nullptr, true, &peak) != HEDIT_OK) return 0;
-  return peak + 4096;
+  const int rc = run(h, nullptr, B, reinterpret_cast<float*>(4096), nullptr, 0, nullptr, true, &peak);
+  return dry_run_bytes(rc, peak);
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
 /* image fp32 [B][3][R][R], CLIP-normalised and resized -> out fp32 [B][embed_dim] (not normalised).  Every argument is
@@ -296,7 +271,7 @@ int hedit_clipimg_encode(hedit_clipimg* h, const float* image, int B, float* out
   ARG_CHECK(h && image && out, "clipimg_encode: null");
   ARG_CHECK(B >= 1 && B <= HEDIT_CLIPIMG_MAX_BATCH, "clipimg_encode: 1 <= B <= 256");
   ARG_CHECK(workspace, "clipimg_encode: null workspace");
-  if (!h->finalized) { hedit_set_error("call hedit_clipimg_finalize after loading the parameters"); return HEDIT_ERR_STATE; }
+  TRY(handle_finalized(h));
   size_t need = 0;
   TRY(run(h, nullptr, B, out, nullptr, 0, nullptr, true, &need));
   TRY(ws_check("clipimg_encode", need, workspace_bytes));

@@ -27,7 +27,7 @@ struct DLevel {
 
 }  // namespace
 
-struct hedit_ddpm : ParamStore {
+struct HEDIT_HANDLE hedit_ddpm : ParamStore {
   hedit_ddpm_cfg cfg;
   int temb_ch = 0;
   bf16_t *t0_w = nullptr, *t1_w = nullptr;
@@ -438,11 +438,7 @@ int check_grad_handle(const hedit_ddpm* h, const char* who) {
     hedit_set_error(std::string(who) + ": this handle has no input-gradient weights (create it with hedit_ddpm_create_grad)");
     return HEDIT_ERR_STATE;
   }
-  if (store_missing(h) != 0) {
-    hedit_set_error("DDPM UNet has " + std::to_string(store_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
-  return HEDIT_OK;
+  return store_require_loaded(h, "DDPM UNet");
 }
 
 void drop_tape(hedit_ddpm* h) {
@@ -451,6 +447,8 @@ void drop_tape(hedit_ddpm* h) {
 }
 
 }  // namespace
+
+HEDIT_LIFECYCLE(ddpm, hedit_ddpm, "DDPM UNet", drop_tape)
 
 // grad: attach the input-gradient twins (hedit_ddpm_create_grad); without it, exactly the forward-only handle
 static int create_impl(const hedit_ddpm_cfg* cfg, hedit_ddpm** out, bool grad) {
@@ -482,7 +480,7 @@ static int create_impl(const hedit_ddpm_cfg* cfg, hedit_ddpm** out, bool grad) {
   h->t1_b = vec(h, "temb.dense.1.bias", tc);
   h->in_w = f32conv(h, "conv_in.weight", ch, cfg->in_channels, 3);
   if (grad) {
-    h->in_t = twin<bf16_t>(h, 2, (size_t)4 * 9 * ch);
+    h->in_t = twin<bf16_t>(h, Pack::Conv3Dgrad, (size_t)4 * 9 * ch);
     if (h->in_t && hipMemset(h->in_t, 0, (size_t)4 * 9 * ch * sizeof(bf16_t)) != hipSuccess) h->alloc_failed = true;
   }
   h->in_b = vec(h, "conv_in.bias", ch);
@@ -501,7 +499,7 @@ static int create_impl(const hedit_ddpm_cfg* cfg, hedit_ddpm** out, bool grad) {
     lv.ch = block_in;
     if (i != L - 1) {
       lv.samp_w = conv3(h, pre + ".downsample.conv.weight", block_in, block_in);
-      if (grad) lv.samp_t = twin<bf16_t>(h, 4, (size_t)block_in * block_in * 9);
+      if (grad) lv.samp_t = twin<bf16_t>(h, Pack::Conv3S2Dgrad, (size_t)block_in * block_in * 9);
       lv.samp_b = vec(h, pre + ".downsample.conv.bias", block_in);
     }
     h->down.push_back(lv);
@@ -524,7 +522,7 @@ static int create_impl(const hedit_ddpm_cfg* cfg, hedit_ddpm** out, bool grad) {
     lv.ch = block_in;
     if (i != 0) {
       lv.samp_w = conv3(h, pre + ".upsample.conv.weight", block_in, block_in);
-      if (grad) lv.samp_t = twin<bf16_t>(h, 2, (size_t)block_in * block_in * 9);
+      if (grad) lv.samp_t = twin<bf16_t>(h, Pack::Conv3Dgrad, (size_t)block_in * block_in * 9);
       lv.samp_b = vec(h, pre + ".upsample.conv.bias", block_in);
     }
     h->up[i] = lv;
@@ -533,18 +531,12 @@ static int create_impl(const hedit_ddpm_cfg* cfg, hedit_ddpm** out, bool grad) {
   h->no_b = vec(h, "norm_out.bias", block_in);
   h->out_w = conv3(h, "conv_out.weight", cfg->out_ch, block_in);
   if (grad) {
-    h->out_t = twin<float>(h, 3, (size_t)cfg->out_ch * block_in * 9);
+    h->out_t = twin<float>(h, Pack::FlipOIHW, (size_t)cfg->out_ch * block_in * 9);
     h->zero_bias = dalloc<float>(h, block_in);
     if (h->zero_bias && hipMemset(h->zero_bias, 0, block_in * sizeof(float)) != hipSuccess) h->alloc_failed = true;
   }
   h->out_b = vec(h, "conv_out.bias", cfg->out_ch);
-  if (h->alloc_failed) {
-    hedit_set_error("hipMalloc failed while creating the DDPM UNet");
-    hedit_ddpm_destroy(h);
-    return HEDIT_ERR_HIP;
-  }
-  *out = h;
-  return HEDIT_OK;
+  return handle_created(h, out);
 }
 
 extern "C" {
@@ -557,37 +549,18 @@ int hedit_ddpm_create_grad(const hedit_ddpm_cfg* cfg, hedit_ddpm** out) try {
   return create_impl(cfg, out, true);
 } catch (...) { return hedit_abi_catch(); }
 
-void hedit_ddpm_destroy(hedit_ddpm* h) try {
-  if (!h) return;
-  drop_tape(h);
-  store_free(h);
-  delete h;
-} catch (...) { (void)hedit_abi_catch(); }
-
-int hedit_ddpm_num_params(const hedit_ddpm* h) { return store_num_params(h); }
-const char* hedit_ddpm_param_name(const hedit_ddpm* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_ddpm_param_shape(const hedit_ddpm* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
-int hedit_ddpm_load(hedit_ddpm* h, const char* name, const float* w, size_t numel, void* stream) try {
-  ARG_CHECK(h && name && w, "null");
-  return store_load(h, "DDPM UNet", name, w, numel, reinterpret_cast<hipStream_t>(stream));
-} catch (...) { return hedit_abi_catch(); }
-int hedit_ddpm_missing(const hedit_ddpm* h) { return h ? store_missing(h) : -1; }
-
 size_t hedit_ddpm_workspace_bytes(hedit_ddpm* h, int B) try {
   if (!h || B < 1) return 0;
   size_t peak = 0;
   const int rc = forward_impl(h, nullptr, 0.f, B, nullptr, nullptr, 0, nullptr, true, &peak);
-  return rc == HEDIT_OK ? peak + 4096 : 0;
+  return dry_run_bytes(rc, peak);
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
 int hedit_ddpm_forward(hedit_ddpm* h, const float* x, float t, int B, float* eps, void* workspace, size_t workspace_bytes,
                        void* stream) try {
   ARG_CHECK(h && x && eps && workspace, "null");
   ARG_CHECK(B >= 1, "B");
-  if (store_missing(h) != 0) {
-    hedit_set_error("DDPM UNet has " + std::to_string(store_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(handle_loaded(h));
   return forward_impl(h, x, t, B, eps, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false, nullptr);
 } catch (...) { return hedit_abi_catch(); }
 
@@ -598,7 +571,7 @@ size_t hedit_ddpm_grad_workspace_bytes(hedit_ddpm* h, int B) try {
   float dummy = 0.f;   // never dereferenced in the dry run
   int rc = forward_keep_impl(h, T, nullptr, 0.f, nullptr);
   if (rc == HEDIT_OK) rc = backward_impl(h, T, &dummy, &dummy);
-  return rc == HEDIT_OK ? T.f.ar.peak + 4096 : 0;
+  return dry_run_bytes(rc, T.f.ar.peak);
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
 int hedit_ddpm_forward_keep(hedit_ddpm* h, const float* x, float t, int B, float* eps, void* workspace, size_t workspace_bytes,

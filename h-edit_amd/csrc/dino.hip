@@ -266,7 +266,7 @@ constexpr EncNames DINO_BLOCK_NAMES = {{".norm1.weight", ".norm1.bias", ".attn.q
 
 }  // namespace
 
-struct hedit_dino : ParamStore {
+struct HEDIT_HANDLE hedit_dino : ParamStore {
   hedit_dino_cfg cfg;
   int L = 0, P = 0;
   int slices = 0;                 // > 0: the attention grid's slice count (hedit_dino_set_slices), else one per pass
@@ -275,7 +275,6 @@ struct hedit_dino : ParamStore {
   std::vector<EncBlock> blocks;   // key_layer whole blocks
   float *kln_g = nullptr, *kln_b = nullptr, *kw = nullptr, *kb = nullptr;      // block key_layer: norm1 and the fused qkv (its key third is used)
   PConv key;
-  bool finalized = false;
 };
 
 namespace {
@@ -289,12 +288,12 @@ int run_keys(hedit_dino* h, PF& f, const float* image, int B, int S, float* keys
   const long Mp = (long)B * (L - 1), M = (long)B * L;
   const float ascale = 0.125f;     // 64^-0.5
   float *img, *X0, *Em, *T;
-  TRY(palloc(f, &img, (size_t)B * 3 * R * R));
+  TRY(aalloc(f, &img, (size_t)B * 3 * R * R));
   if (!dry) { hipLaunchKernelGGL(prep_kernel, egrid((long)B * 3 * R * R), dim3(256), 0, st, image, img, B, S, R); LAUNCH_CHECK(); }
-  TRY(palloc(f, &X0, (size_t)Mp * K0));
+  TRY(aalloc(f, &X0, (size_t)Mp * K0));
   if (!dry) TRY(enc_patchify_launch(img, X0, B, R, p, 0, st));
   TRY(lin(f, X0, K0, P_COPY, nullptr, nullptr, h->conv, false, Mp, &Em));
-  TRY(palloc(f, &T, (size_t)M * W));
+  TRY(aalloc(f, &T, (size_t)M * W));
   if (!dry) TRY(enc_tokens_launch(Em, h->conv_b, h->cls, h->pos, T, B, L, W, st));
   f.ar.free(Em);
   f.ar.free(X0);
@@ -307,7 +306,7 @@ int run_keys(hedit_dino* h, PF& f, const float* image, int B, int S, float* keys
   for (const EncBlock& k : h->blocks) TRY(enc_block_forward(f, k, T, M, W, P_GELU, LN_EPS, attn));      // exact (erf) GELU
   // block key_layer: norm1 and the key third of qkv
   float *a, *raw;
-  TRY(palloc(f, &a, (size_t)M * W));
+  TRY(aalloc(f, &a, (size_t)M * W));
   TRY(ln(f, T, h->kln_g, h->kln_b, M, W, LN_EPS, a));
   TRY(lin(f, a, W, P_COPY, nullptr, nullptr, h->key, false, M, &raw));
   if (!dry) TRY(enc_add_bias_res_launch(raw, h->kb + W, nullptr, keys, M * W, W, st));      // out = raw + bias: the keys
@@ -332,10 +331,10 @@ int run_dist(hedit_dino* h, const float* a, const float* b, int N, int S, float*
   const size_t one = (size_t)N * 3 * S * S;
   const int T = cdiv(L, 32);
   float *both, *keys, *nrm, *part;
-  TRY(palloc(f, &keys, (size_t)2 * N * L * W));
-  TRY(palloc(f, &nrm, (size_t)2 * N * L));
-  TRY(palloc(f, &part, (size_t)N * T * T));
-  TRY(palloc(f, &both, 2 * one));
+  TRY(aalloc(f, &keys, (size_t)2 * N * L * W));
+  TRY(aalloc(f, &nrm, (size_t)2 * N * L));
+  TRY(aalloc(f, &part, (size_t)N * T * T));
+  TRY(aalloc(f, &both, 2 * one));
   if (!dry) {
     HIP_TRY(hipMemcpyAsync(both, a, one * sizeof(float), hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipMemcpyAsync(both + one, b, one * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -360,6 +359,8 @@ int run_dist(hedit_dino* h, const float* a, const float* b, int N, int S, float*
 
 }  // namespace
 
+HEDIT_LIFECYCLE(dino, hedit_dino, "DINO ViT", no_pre_destroy)
+
 extern "C" {
 
 int hedit_dino_create(const hedit_dino_cfg* cfg, hedit_dino** out) try {
@@ -378,9 +379,9 @@ int hedit_dino_create(const hedit_dino_cfg* cfg, hedit_dino** out) try {
   const int W = cfg->width, p = cfg->patch_size;
   {
     h->cls = dalloc<float>(h, W);
-    add_slot(h, "cls_token", 0, h->cls, W, 0, 0, 3, 1, 1, W, 1);
+    add_slot(h, "cls_token", Pack::F32, h->cls, W, 0, 0, 3, 1, 1, W, 1);
     h->pos = dalloc<float>(h, (size_t)L * W);
-    add_slot(h, "pos_embed", 0, h->pos, (size_t)L * W, 0, 0, 3, 1, L, W, 1);
+    add_slot(h, "pos_embed", Pack::F32, h->pos, (size_t)L * W, 0, 0, 3, 1, L, W, 1);
   }
   h->conv_w = f32conv(h, "patch_embed.proj.weight", W, 3, p);
   h->conv_b = vec(h, "patch_embed.proj.bias", W);
@@ -391,38 +392,12 @@ int hedit_dino_create(const hedit_dino_cfg* cfg, hedit_dino** out) try {
     h->kln_g = vec(h, pre + n.s[0], W); h->kln_b = vec(h, pre + n.s[1], W);
     h->kw = mat(h, pre + n.s[2], 3 * W, W); h->kb = vec(h, pre + n.s[3], 3 * W);
   }
-  if (h->alloc_failed) {
-    hedit_set_error("hipMalloc failed while creating the DINO ViT");
-    store_free(h);
-    delete h;
-    return HEDIT_ERR_HIP;
-  }
-  *out = h;
-  return HEDIT_OK;
+  return handle_created(h, out);
 } catch (...) { return hedit_abi_catch(); }
-
-void hedit_dino_destroy(hedit_dino* h) try {
-  if (!h) return;
-  store_free(h);
-  delete h;
-} catch (...) { (void)hedit_abi_catch(); }
-
-int hedit_dino_num_params(const hedit_dino* h) { return store_num_params(h); }
-const char* hedit_dino_param_name(const hedit_dino* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_dino_param_shape(const hedit_dino* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
-int hedit_dino_load(hedit_dino* h, const char* name, const float* w, size_t numel, void* stream) try {
-  ARG_CHECK(h && name && w, "null");
-  h->finalized = false;
-  return store_load(h, "DINO ViT", name, w, numel, reinterpret_cast<hipStream_t>(stream));
-} catch (...) { return hedit_abi_catch(); }
-int hedit_dino_missing(const hedit_dino* h) { return h ? store_missing(h) : -1; }
 
 int hedit_dino_finalize(hedit_dino* h, void* stream) try {
   ARG_CHECK(h, "null");
-  if (store_missing(h) != 0) {
-    hedit_set_error("DINO ViT has " + std::to_string(store_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(handle_loaded(h));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int W = h->cfg.width, p = h->cfg.patch_size;
   TRY(pack_fwd(h, h->conv, h->conv_w, W, 3 * p * p, false, st));
@@ -448,15 +423,15 @@ int hedit_dino_set_slices(hedit_dino* h, int slices) try {
 size_t hedit_dino_workspace_bytes(hedit_dino* h, int N, int S) try {
   if (!h || N < 1 || N > HEDIT_DINO_MAX_PAIRS || S < h->cfg.patch_size || S > MAX_SIDE) return 0;
   size_t peak = 0;
-  if (run_dist(h, nullptr, nullptr, N, S, nullptr, nullptr, 0, nullptr, true, &peak) != HEDIT_OK) return 0;
-  return peak + 4096;
+  const int rc = run_dist(h, nullptr, nullptr, N, S, nullptr, nullptr, 0, nullptr, true, &peak);
+  return dry_run_bytes(rc, peak);
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
 /* image fp32 [B][3][S][S], 0..255 scale, already multiplied by its mask -> keys fp32 [B][L][W] of block key_layer (bias
  * included).  Every argument is checked before the first launch. */
 int hedit_dino_keys(hedit_dino* h, const float* image, int B, int S, float* keys, void* workspace, size_t workspace_bytes, void* stream) try {
   ARG_CHECK(h && image && keys, "dino_keys: null");
-  if (!h->finalized) { hedit_set_error("call hedit_dino_finalize after loading the parameters"); return HEDIT_ERR_STATE; }
+  TRY(handle_finalized(h));
   ARG_CHECK(B >= 1 && B <= 2 * HEDIT_DINO_MAX_PAIRS, "dino_keys: 1 <= B <= 128");
   ARG_CHECK(S >= h->cfg.patch_size && S <= MAX_SIDE, "dino_keys: S must be in [patch_size, 4096]");
   ARG_CHECK(workspace, "dino_keys: null workspace");
@@ -471,7 +446,7 @@ int hedit_dino_keys(hedit_dino* h, const float* image, int B, int S, float* keys
 int hedit_dino_structure_distance(hedit_dino* h, const float* a, const float* b, int N, int S, float* dist, void* workspace, size_t workspace_bytes,
                                   void* stream) try {
   ARG_CHECK(h && a && b && dist, "dino_structure_distance: null");
-  if (!h->finalized) { hedit_set_error("call hedit_dino_finalize after loading the parameters"); return HEDIT_ERR_STATE; }
+  TRY(handle_finalized(h));
   ARG_CHECK(N >= 1 && N <= HEDIT_DINO_MAX_PAIRS, "dino_structure_distance: 1 <= N <= 64");
   ARG_CHECK(S >= h->cfg.patch_size && S <= MAX_SIDE, "dino_structure_distance: S must be in [patch_size, 4096]");
   ARG_CHECK(workspace, "dino_structure_distance: null workspace");

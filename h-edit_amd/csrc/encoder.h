@@ -60,8 +60,6 @@ int enc_pack_block(ParamStore* h, EncBlock& k, int W, bool fwd_only, hipStream_t
   return HEDIT_OK;
 }
 
-inline dim3 egrid(long total) { return dim3(ew_grid(total)); }
-
 PF make_pf(int B, void* ws, size_t ws_bytes, hipStream_t st, bool dry) {
   PF f{B, st, Arena{}};
   f.ar.dry = dry;
@@ -102,26 +100,26 @@ int lin(PF& f, const float* x, int C, int op, const float* q, const float* z, co
 template <class Attn>
 int enc_block_forward(PF& f, const EncBlock& k, float*& T, long M, int W, int act_op, float eps, Attn attn) {
   float *a, *qkv, *A, *raw, *Tmid, *m, *H, *Tn;
-  TRY(palloc(f, &a, (size_t)M * W));
+  TRY(aalloc(f, &a, (size_t)M * W));
   TRY(ln(f, T, k.ln1g, k.ln1b, M, W, eps, a));
   TRY(lin(f, a, W, P_COPY, nullptr, nullptr, k.in, false, M, &qkv));
   f.ar.free(a);
-  TRY(palloc(f, &A, (size_t)M * W));
+  TRY(aalloc(f, &A, (size_t)M * W));
   if (!f.dry()) TRY(attn(qkv, k.bin, A));
   f.ar.free(qkv);
   TRY(lin(f, A, W, P_COPY, nullptr, nullptr, k.out, false, M, &raw));
   f.ar.free(A);
-  TRY(palloc(f, &Tmid, (size_t)M * W));
+  TRY(aalloc(f, &Tmid, (size_t)M * W));
   if (!f.dry()) TRY(enc_add_bias_res_launch(raw, k.bo, T, Tmid, M * W, W, f.st));
   f.ar.free(raw);
   f.ar.free(T);
-  TRY(palloc(f, &m, (size_t)M * W));
+  TRY(aalloc(f, &m, (size_t)M * W));
   TRY(ln(f, Tmid, k.ln2g, k.ln2b, M, W, eps, m));
   TRY(lin(f, m, W, P_COPY, nullptr, nullptr, k.fc, false, M, &H));
   f.ar.free(m);
   TRY(lin(f, H, 4 * W, act_op, k.bfc, nullptr, k.proj, false, M, &raw));      // act(H + bias) as the operand op
   f.ar.free(H);
-  TRY(palloc(f, &Tn, (size_t)M * W));
+  TRY(aalloc(f, &Tn, (size_t)M * W));
   if (!f.dry()) TRY(enc_add_bias_res_launch(raw, k.bp, Tmid, Tn, M * W, W, f.st));
   f.ar.free(raw);
   f.ar.free(Tmid);

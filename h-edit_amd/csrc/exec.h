@@ -1,8 +1,21 @@
-// Pieces shared by the network executors (unet.hip, vae.hip).
+// Pieces shared by every network executor: the TRY / RUN macros, the workspace arena and its allocator, the element-wise
+// launch grid and the answer of a *_workspace_bytes dry run.
 #pragma once
 #include <map>
 
 #include "common.h"
+
+#define TRY(expr)                        \
+  do {                                   \
+    int _rc = (expr);                    \
+    if (_rc != HEDIT_OK) return _rc;     \
+  } while (0)
+
+// launch unless the executor context `f` is planning its workspace
+#define RUN(f, expr)            \
+  do {                          \
+    if (!(f).dry()) TRY(expr);  \
+  } while (0)
 
 namespace {
 
@@ -34,5 +47,25 @@ struct Arena {
   }
 };
 
+inline Arena& arena_of(Arena& a) { return a; }
+template <class F>
+auto arena_of(F& f) -> decltype((f.ar)) { return f.ar; }
+
+// n elements of T from an Arena, or from the arena `ar` of an executor context
+template <class F, class T>
+int aalloc(F& f, T** out, size_t n) {
+  Arena& ar = arena_of(f);
+  *out = reinterpret_cast<T*>(ar.alloc(n * sizeof(T)));
+  if (!*out) {
+    hedit_set_error("workspace too small (need more than " + std::to_string(ar.cap) + " bytes)");
+    return HEDIT_ERR_ARG;
+  }
+  return HEDIT_OK;
+}
+
+// what a *_workspace_bytes entry answers after its dry run: the arena's peak plus slack, 0 if the walk failed
+inline size_t dry_run_bytes(int rc, size_t peak) { return rc == HEDIT_OK ? peak + 4096 : 0; }
+
+inline dim3 egrid(long total) { return dim3(ew_grid(total)); }
 
 }  // namespace

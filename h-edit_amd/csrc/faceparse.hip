@@ -24,8 +24,6 @@ constexpr int FP_FILTERS[FP_LEVELS] = {16, 32, 64, 128, 256};   // [64, 128, 256
 constexpr int FP_CLASSES = 19;
 constexpr int FP_MAX_KSIZE = 31;                                  // SoftErosion kernel_size bound of hedit_face_mask
 
-static inline dim3 egrid(long total) { return dim3(ew_grid(total)); }
-
 // ------------------------------------------------------------------------------------------------ network kernels
 // image NCHW [B][C][HW] -> NHWC rows [B*HW][C]
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restrict__ x, float* __restrict__ y, int C, int HW, long total) {
@@ -286,11 +284,10 @@ struct FUp {
 
 }  // namespace
 
-struct hedit_faceparse : ParamStore {
+struct HEDIT_HANDLE hedit_faceparse : ParamStore {
   FBlock enc[FP_LEVELS];             // conv1 .. conv4, center
   FUp up[FP_LEVELS - 1];             // up[l] = up_concat{l+1}: output at level l
   float *fw = nullptr, *fb = nullptr;
-  bool finalized = false;
 };
 
 namespace {
@@ -333,7 +330,7 @@ int op_split_ld(PF& f, const float* x, int C, int ldx, int op, const float* p, c
   Split3Params s{};
   s.x = x; s.ldx = ldx; s.p = p; s.q = q; s.pq_img = pq_img; s.op = op;
   s.Kp = split_kp(C); s.Cs = split_cs(C); s.C = C; s.geo = 0; s.B = f.B; s.H = H; s.W = W;
-  TRY(palloc(f, out, (size_t)rows * s.Kp));
+  TRY(aalloc(f, out, (size_t)rows * s.Kp));
   s.out = *out;
   if (!f.dry()) TRY(split3_launch(s, rows, f.st));
   return HEDIT_OK;
@@ -366,9 +363,9 @@ int conv_bn(PF& f, const FConv& c, const bf16_t* A, int H, int W, bool batch_sta
     int cw = 1;
     while (cw < C && cw < 64) cw *= 2;
     float* part;
-    TRY(palloc(f, &part, (size_t)B * nslab * C * 3));
-    TRY(palloc(f, &a.p, (size_t)B * C));
-    TRY(palloc(f, &a.q, (size_t)B * C));
+    TRY(aalloc(f, &part, (size_t)B * nslab * C * 3));
+    TRY(aalloc(f, &a.p, (size_t)B * C));
+    TRY(aalloc(f, &a.q, (size_t)B * C));
     if (!f.dry()) {
       hipLaunchKernelGGL(bn_stats_part_kernel, dim3(cdiv(C, cw), B, nslab), dim3(256), 0, f.st, a.z, C, C, HW, nslab, cw, part);
       LAUNCH_CHECK();
@@ -409,9 +406,9 @@ int run(hedit_faceparse* h, const float* image, int B, int H, int W, bool batch_
   f.ar.base = reinterpret_cast<char*>(ws);
   f.ar.cap = ws_bytes;
   float* cat[FP_LEVELS - 1];            // [B][H_l][W_l][2 F_l]: [skip | up]
-  for (int l = 0; l < FP_LEVELS - 1; ++l) TRY(palloc(f, &cat[l], (size_t)B * (H >> l) * (W >> l) * 2 * FP_FILTERS[l]));
+  for (int l = 0; l < FP_LEVELS - 1; ++l) TRY(aalloc(f, &cat[l], (size_t)B * (H >> l) * (W >> l) * 2 * FP_FILTERS[l]));
   float* X;
-  TRY(palloc(f, &X, (size_t)B * H * W * 3));
+  TRY(aalloc(f, &X, (size_t)B * H * W * 3));
   if (!dry) {
     const long n = (long)B * H * W * 3;
     hipLaunchKernelGGL(nchw_to_nhwc_kernel, egrid(n), dim3(256), 0, st, image, X, 3, H * W, n);
@@ -423,7 +420,7 @@ int run(hedit_faceparse* h, const float* image, int B, int H, int W, bool batch_
     const int Hl = H >> l, Wl = W >> l, F = FP_FILTERS[l];
     TRY(block_fwd(f, h->enc[l], X, ldx, Hl, Wl, batch_stats, &a));
     f.ar.free(X);
-    TRY(palloc(f, &X, (size_t)B * (Hl / 2) * (Wl / 2) * F));
+    TRY(aalloc(f, &X, (size_t)B * (Hl / 2) * (Wl / 2) * F));
     if (!dry) {
       hipLaunchKernelGGL(affine_relu_pool_kernel, egrid((long)B * (Hl / 2) * (Wl / 2) * F), dim3(256), 0, st, a.z, a.P(), a.Q(), a.pq_img,
                          cat[l], 2 * F, X, B, Hl, Wl, F);
@@ -476,6 +473,8 @@ size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
 }  // namespace
 
+HEDIT_LIFECYCLE(faceparse, hedit_faceparse, "face parsing", no_pre_destroy)
+
 extern "C" {
 
 int hedit_faceparse_create(hedit_faceparse** out) try {
@@ -492,45 +491,18 @@ int hedit_faceparse_create(hedit_faceparse** out) try {
     u.cout = FP_FILTERS[l];
     u.conv = make_fblock(h, pre + ".conv", u.cin, u.cout);
     u.w = dalloc<float>(h, (size_t)u.cin * u.cout * 4);
-    add_slot(h, pre + ".up.weight", 0, u.w, (size_t)u.cin * u.cout * 4, u.cin, u.cout, 4, u.cin, u.cout, 2, 2);
+    add_slot(h, pre + ".up.weight", Pack::F32, u.w, (size_t)u.cin * u.cout * 4, u.cin, u.cout, 4, u.cin, u.cout, 2, 2);
     u.bias = vec(h, pre + ".up.bias", u.cout);
     u.wg = dalloc<float>(h, (size_t)u.cin * u.cout * 4);
   }
   h->fw = f32conv(h, "final.weight", FP_CLASSES, FP_FILTERS[0], 1);
   h->fb = vec(h, "final.bias", FP_CLASSES);
-  if (h->alloc_failed) {
-    hedit_set_error("hipMalloc failed while creating the face-parsing network");
-    store_free(h);
-    delete h;
-    return HEDIT_ERR_HIP;
-  }
-  *out = h;
-  return HEDIT_OK;
+  return handle_created(h, out);
 } catch (...) { return hedit_abi_catch(); }
 
-void hedit_faceparse_destroy(hedit_faceparse* h) try {
-  if (!h) return;
-  store_free(h);
-  delete h;
-} catch (...) { (void)hedit_abi_catch(); }
-
-int hedit_faceparse_num_params(const hedit_faceparse* h) { return store_num_params(h); }
-const char* hedit_faceparse_param_name(const hedit_faceparse* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_faceparse_param_shape(const hedit_faceparse* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
-int hedit_faceparse_load(hedit_faceparse* h, const char* name, const float* w, size_t numel, void* stream) try {
-  ARG_CHECK(h && name && w, "null");
-  h->finalized = false;
-  return store_load(h, "face parsing", name, w, numel, reinterpret_cast<hipStream_t>(stream));
-} catch (...) { return hedit_abi_catch(); }
-int hedit_faceparse_missing(const hedit_faceparse* h) { return h ? store_missing(h) : -1; }
-
-/* pack the split-bf16 GEMM operands and the eval-mode BatchNorm affines; call once after loading */
 int hedit_faceparse_finalize(hedit_faceparse* h, void* stream) try {
   ARG_CHECK(h, "null");
-  if (store_missing(h) != 0) {
-    hedit_set_error("face parsing has " + std::to_string(store_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(handle_loaded(h));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   auto conv = [&](FConv& c) -> int {
     TRY(bn_fold_bias_launch(c.bias, c.bn.g, c.bn.b, c.bn.m, c.bn.v, FP_BN_EPS, c.pe, c.qe, c.cout, st));
@@ -553,8 +525,8 @@ int hedit_faceparse_finalize(hedit_faceparse* h, void* stream) try {
 size_t hedit_faceparse_workspace_bytes(hedit_faceparse* h, int B, int H, int W) try {
   if (!h || !h->finalized || shape_check(B, H, W) != HEDIT_OK) return 0;      // the GEMM geometry is set by finalize
   size_t peak = 0;
-  if (run(h, nullptr, B, H, W, true, nullptr, nullptr, 0, nullptr, true, &peak) != HEDIT_OK) return 0;
-  return peak + 4096;
+  const int rc = run(h, nullptr, B, H, W, true, nullptr, nullptr, 0, nullptr, true, &peak);
+  return dry_run_bytes(rc, peak);
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
 /* image fp32 [B][3][H][W] in [-1, 1] -> labels int64 [B][1][H][W] = argmax of the 19 class logits */
@@ -562,7 +534,7 @@ int hedit_faceparse_labels(hedit_faceparse* h, const float* image, int B, int H,
                            size_t workspace_bytes, void* stream) try {
   ARG_CHECK(h && image && labels && workspace, "faceparse_labels args");
   TRY(shape_check(B, H, W));
-  if (!h->finalized) { hedit_set_error("call hedit_faceparse_finalize after loading the parameters"); return HEDIT_ERR_STATE; }
+  TRY(handle_finalized(h));
   return run(h, image, B, H, W, batch_stats != 0, labels, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false, nullptr);
 } catch (...) { return hedit_abi_catch(); }
 

@@ -29,7 +29,7 @@ struct IUnit {
 
 }  // namespace
 
-struct hedit_irse : ParamStore {
+struct HEDIT_HANDLE hedit_irse : ParamStore {
   float *in_w = nullptr, *in_prelu = nullptr, *in_p = nullptr, *in_q = nullptr;
   BN in_bn{}, out_bn2{}, out_bn1{};
   PConv in_c, lin;
@@ -37,7 +37,6 @@ struct hedit_irse : ParamStore {
   float *lin_w = nullptr, *lin_b = nullptr;
   float *out_p = nullptr, *out_q = nullptr;          // BatchNorm2d in front of the flatten, tiled over the 49 pixels
   float *lin_p = nullptr, *lin_q = nullptr;          // Linear bias + BatchNorm1d folded
-  bool finalized = false;
 };
 
 namespace {
@@ -65,9 +64,9 @@ int unit_fwd(PF& f, const IUnit& u, const float* X, int H, int W, float** Yout, 
   TRY(op_split(f, z1, u.depth, P_PRELU, u.prelu, nullptr, 0, nullptr, 0, H, W, M, &A2));      // PReLU -> conv2 operand
   TRY(pgemm(f, A2, u.c2, false, u.stride == 2 ? 2 : 1, H, W, M2, &uu));                       // BatchNorm folded: u + q2
   f.ar.free(A2);
-  TRY(palloc(f, &pool, (size_t)B * se_nslab(Ho * Wo) * u.depth));
-  TRY(palloc(f, &hb, (size_t)B * (u.depth / 16)));
-  TRY(palloc(f, &sb, (size_t)B * u.depth));
+  TRY(aalloc(f, &pool, (size_t)B * se_nslab(Ho * Wo) * u.depth));
+  TRY(aalloc(f, &hb, (size_t)B * (u.depth / 16)));
+  TRY(aalloc(f, &sb, (size_t)B * u.depth));
   if (!f.dry()) {
     TRY(se_pool_launch(uu, pool, B, Ho * Wo, u.depth, f.st));
     TRY(se_fc_launch(pool, u.q2, u.fc1, u.fc2, hb, sb, B, Ho * Wo, u.depth, u.depth / 16, f.st));
@@ -78,7 +77,7 @@ int unit_fwd(PF& f, const IUnit& u, const float* X, int H, int W, float** Yout, 
     TRY(pgemm(f, A3, u.sc, false, 0, Ho, Wo, M2, &sc));
     f.ar.free(A3);
   }
-  TRY(palloc(f, &Y, (size_t)M2 * u.depth));
+  TRY(aalloc(f, &Y, (size_t)M2 * u.depth));
   if (!f.dry()) TRY(se_combine_launch(uu, u.q2, sb, sc, u.qsc, X, u.stride, Y, B, Ho, Wo, u.depth, f.st));
   if (sc) f.ar.free(sc);
   *tape = UnitTape{const_cast<float*>(X), z1, uu, sb, hb, H, W};
@@ -92,8 +91,8 @@ int unit_bwd(PF& f, const IUnit& u, const UnitTape& t, const float* dY, float** 
   const long M = (long)B * H * W, M2 = (long)B * Ho * Wo;
   float *gs, *rb, *dz, *dxa, *dsc = nullptr, *dX;
   bf16_t *A, *A2, *A3;
-  TRY(palloc(f, &gs, (size_t)B * se_nslab(Ho * Wo) * u.depth));
-  TRY(palloc(f, &rb, (size_t)B * u.depth));
+  TRY(aalloc(f, &gs, (size_t)B * se_nslab(Ho * Wo) * u.depth));
+  TRY(aalloc(f, &rb, (size_t)B * u.depth));
   if (!f.dry()) {
     TRY(se_bwd_reduce_launch(dY, t.u, u.q2, gs, B, Ho * Wo, u.depth, f.st));
     TRY(se_fc_bwd_launch(gs, t.s, t.hb, u.fc1, u.fc2, rb, B, u.depth, u.depth / 16, Ho * Wo, f.st));
@@ -115,7 +114,7 @@ int unit_bwd(PF& f, const IUnit& u, const UnitTape& t, const float* dY, float** 
     f.ar.free(A3);
     dshort = dsc;
   }
-  TRY(palloc(f, &dX, (size_t)M * u.cin));
+  TRY(aalloc(f, &dX, (size_t)M * u.cin));
   if (!f.dry()) TRY(unit_bwd_combine_launch(dxa, u.p1, dshort, u.stride, dX, B, H, W, u.cin, f.st));
   f.ar.free(dxa);
   if (dsc) f.ar.free(dsc);
@@ -134,13 +133,13 @@ int run(hedit_irse* h, const float* image, const float* ref, int ref_stride, int
   const long M0 = (long)B * 112 * 112;
   float *a0, *z0, *x0;
   bf16_t* A;
-  TRY(palloc(f, &a0, (size_t)M0 * 3));
+  TRY(aalloc(f, &a0, (size_t)M0 * 3));
   if (!dry) TRY(face_pool_launch(image, a0, B, st));
   TRY(op_split(f, a0, 3, P_COPY, nullptr, nullptr, 0, nullptr, 0, 112, 112, M0, &A));
   f.ar.free(a0);
   TRY(pgemm(f, A, h->in_c, false, 1, 112, 112, M0, &z0));          // BatchNorm folded into the weights: z0 + in_q
   f.ar.free(A);
-  TRY(palloc(f, &x0, (size_t)M0 * 64));
+  TRY(aalloc(f, &x0, (size_t)M0 * 64));
   if (!dry) TRY(act_launch(z0, h->in_prelu, h->in_q, x0, M0 * 64, 64, P_PRELU, st));
   std::vector<UnitTape> tapes(h->units.size());
   float* X = x0;
@@ -162,7 +161,7 @@ int run(hedit_irse* h, const float* image, const float* ref, int ref_stride, int
   TRY(op_split(f, X, K, P_AFFINE, h->out_p, h->out_q, 0, nullptr, 0, 1, 1, B, &A));
   TRY(pgemm(f, A, h->lin, false, 0, 1, 1, B, &fr));
   f.ar.free(A);
-  if (grad) TRY(palloc(f, &df, (size_t)B * 512));
+  if (grad) TRY(aalloc(f, &df, (size_t)B * 512));
   if (!dry) TRY(cos_head_launch(fr, h->lin_q, ref, ref_stride, feat, loss, grad ? df : nullptr, B, 512, scale, st));
   f.ar.free(fr);
   if (grad) {
@@ -171,7 +170,7 @@ int run(hedit_irse* h, const float* image, const float* ref, int ref_stride, int
     TRY(pgemm(f, A, h->lin, true, 0, 1, 1, B, &dflat));
     f.ar.free(A);
     f.ar.free(df);
-    TRY(palloc(f, &dX, (size_t)B * K));
+    TRY(aalloc(f, &dX, (size_t)B * K));
     if (!dry) TRY(scale_cols_launch(dflat, h->out_p, dX, (long)B * K, K, st));
     f.ar.free(dflat);
     f.ar.free(X);
@@ -201,6 +200,8 @@ int run(hedit_irse* h, const float* image, const float* ref, int ref_stride, int
 }
 
 }  // namespace
+
+HEDIT_LIFECYCLE(irse50, hedit_irse, "IR-SE50", no_pre_destroy)
 
 extern "C" {
 
@@ -240,45 +241,18 @@ int hedit_irse50_create(hedit_irse** out) try {
   }
   h->out_bn2 = make_bn(h, "output_layer.0", 512);
   h->lin_w = dalloc<float>(h, (size_t)512 * 25088);
-  add_slot(h, "output_layer.3.weight", 0, h->lin_w, (size_t)512 * 25088, 512, 25088, 2, 512, 25088, 1, 1);
+  add_slot(h, "output_layer.3.weight", Pack::F32, h->lin_w, (size_t)512 * 25088, 512, 25088, 2, 512, 25088, 1, 1);
   h->lin_b = vec(h, "output_layer.3.bias", 512);
   h->out_bn1 = make_bn(h, "output_layer.4", 512);
   h->in_p = dalloc<float>(h, 64); h->in_q = dalloc<float>(h, 64);
   h->out_p = dalloc<float>(h, 25088); h->out_q = dalloc<float>(h, 25088);
   h->lin_p = dalloc<float>(h, 512); h->lin_q = dalloc<float>(h, 512);
-  if (h->alloc_failed) {
-    hedit_set_error("hipMalloc failed while creating the IR-SE50 backbone");
-    store_free(h);
-    delete h;
-    return HEDIT_ERR_HIP;
-  }
-  *out = h;
-  return HEDIT_OK;
+  return handle_created(h, out);
 } catch (...) { return hedit_abi_catch(); }
 
-void hedit_irse50_destroy(hedit_irse* h) try {
-  if (!h) return;
-  store_free(h);
-  delete h;
-} catch (...) { (void)hedit_abi_catch(); }
-
-int hedit_irse50_num_params(const hedit_irse* h) { return store_num_params(h); }
-const char* hedit_irse50_param_name(const hedit_irse* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_irse50_param_shape(const hedit_irse* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
-int hedit_irse50_load(hedit_irse* h, const char* name, const float* w, size_t numel, void* stream) try {
-  ARG_CHECK(h && name && w, "null");
-  h->finalized = false;
-  return store_load(h, "IR-SE50", name, w, numel, reinterpret_cast<hipStream_t>(stream));
-} catch (...) { return hedit_abi_catch(); }
-int hedit_irse50_missing(const hedit_irse* h) { return h ? store_missing(h) : -1; }
-
-/* fold the BatchNorms and build the split-bf16 GEMM operands (forward and input-gradient); call once after loading */
 int hedit_irse50_finalize(hedit_irse* h, void* stream) try {
   ARG_CHECK(h, "null");
-  if (store_missing(h) != 0) {
-    hedit_set_error("IR-SE50 has " + std::to_string(store_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(handle_loaded(h));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   TRY(bn_affine_launch(h->in_bn.g, h->in_bn.b, h->in_bn.m, h->in_bn.v, BN_EPS, h->in_p, h->in_q, 64, 1, st));
   TRY(make_pconv(h, h->in_c, h->in_w, h->in_p, 64, 3, 3, 0, 0, st));
@@ -305,15 +279,15 @@ int hedit_irse50_finalize(hedit_irse* h, void* stream) try {
 size_t hedit_irse50_workspace_bytes(hedit_irse* h, int B) try {
   if (!h || B < 1) return 0;
   size_t peak = 0;
-  if (run(h, nullptr, nullptr, 0, B, nullptr, nullptr, nullptr, 1.f, nullptr, 0, nullptr, true, &peak) != HEDIT_OK) return 0;
-  return peak + 4096;
+  const int rc = run(h, nullptr, nullptr, 0, B, nullptr, nullptr, nullptr, 1.f, nullptr, 0, nullptr, true, &peak);
+  return dry_run_bytes(rc, peak);
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
 /* image fp32 [B][3][256][256] in [-1, 1] -> feat fp32 [B][512], the l2-normalised identity feature
  * (IDLoss.extract_feats followed by F.normalize, arcface_model.py:40-52) */
 int hedit_irse50_features(hedit_irse* h, const float* image, int B, float* feat, void* workspace, size_t workspace_bytes, void* stream) try {
   ARG_CHECK(h && image && feat && workspace && B >= 1, "irse50_features args");
-  if (!h->finalized) { hedit_set_error("call hedit_irse50_finalize after loading the parameters"); return HEDIT_ERR_STATE; }
+  TRY(handle_finalized(h));
   return run(h, image, nullptr, 0, B, feat, nullptr, nullptr, 1.f, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false, nullptr);
 } catch (...) { return hedit_abi_catch(); }
 
@@ -323,7 +297,7 @@ int hedit_irse50_features(hedit_irse* h, const float* image, int B, float* feat,
 int hedit_irse50_cos_fwd_bwd(hedit_irse* h, const float* image, const float* ref_feat, int ref_per_image, int B, float scale,
                              float* loss, float* d_image, void* workspace, size_t workspace_bytes, void* stream) try {
   ARG_CHECK(h && image && ref_feat && loss && d_image && workspace && B >= 1, "irse50_cos_fwd_bwd args");
-  if (!h->finalized) { hedit_set_error("call hedit_irse50_finalize after loading the parameters"); return HEDIT_ERR_STATE; }
+  TRY(handle_finalized(h));
   return run(h, image, ref_feat, ref_per_image ? 512 : 0, B, nullptr, loss, d_image, scale, workspace, workspace_bytes,
              reinterpret_cast<hipStream_t>(stream), false, nullptr);
 } catch (...) { return hedit_abi_catch(); }

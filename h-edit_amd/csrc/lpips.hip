@@ -23,13 +23,12 @@ inline int tap_of(int l) { return l == 1 ? 0 : (l == 3 ? 1 : (l == 6 ? 2 : (l ==
 
 }  // namespace
 
-struct hedit_lpips : ParamStore {
+struct HEDIT_HANDLE hedit_lpips : ParamStore {
   float* w[VGG_N] = {};
   float* b[VGG_N] = {};
   PConv conv[VGG_N];
   float* lin[5] = {};
   float shift[3] = {-0.030f, -0.088f, -0.188f}, scale[3] = {0.458f, 0.448f, 0.450f};   // lpips ScalingLayer buffers
-  bool finalized = false;
 };
 
 namespace {
@@ -59,7 +58,7 @@ int run(hedit_lpips* h, const float* x, const float* src, long src_stride, int B
   const bool grad = want_grad;
   const size_t per_img = feature_floats(H0, W0);
   float* a0;
-  TRY(palloc(f, &a0, (size_t)B * H0 * W0 * 3));
+  TRY(aalloc(f, &a0, (size_t)B * H0 * W0 * 3));
   if (!dry) TRY(lpips_prep_launch(x, a0, h->shift, h->scale, B, H0, W0, st));
   LTape tp[VGG_N] = {};
   float* headG[5] = {};            // gradient of the objective w.r.t. the tap's feature map F (fp32), kept until the backward reaches it
@@ -85,8 +84,8 @@ int run(hedit_lpips* h, const float* x, const float* src, long src_stride, int B
       const int HW = H * W;
       float *dpix = nullptr, *dF = nullptr;
       if (src) {
-        TRY(palloc(f, &dpix, (size_t)M));
-        if (grad) TRY(palloc(f, &dF, (size_t)M * cout));
+        TRY(aalloc(f, &dpix, (size_t)M));
+        if (grad) TRY(aalloc(f, &dF, (size_t)M * cout));
         if (!dry) {
           TRY(lpips_head_launch(z, h->b[l], src + foff, src_stride, h->lin[t], nullptr, dpix, dF, B, HW, cout, scale / (float)HW, st));
           TRY(lpips_reduce_launch(dpix, loss, B, HW, t == 0 ? 1 : 0, st));
@@ -101,8 +100,8 @@ int run(hedit_lpips* h, const float* x, const float* src, long src_stride, int B
       }
       foff += (size_t)HW * cout;
       if (t < 4) {
-        TRY(palloc(f, &tp[l].zp, (size_t)M / 4 * cout));
-        TRY(palloc(f, &tp[l].idx, (size_t)M / 4 * cout));
+        TRY(aalloc(f, &tp[l].zp, (size_t)M / 4 * cout));
+        TRY(aalloc(f, &tp[l].idx, (size_t)M / 4 * cout));
         if (!dry) TRY(maxpool2_launch(z, tp[l].zp, tp[l].idx, B, H, W, cout, st));
         if (!grad) { f.ar.free(z); f.ar.free(tp[l].idx); }
         in = tp[l].zp;
@@ -138,7 +137,7 @@ int run(hedit_lpips* h, const float* x, const float* src, long src_stride, int B
       // the input was pool(relu(z_{l-1} + b)): scatter to the winners and add the tap's own gradient
       const LTape& pl = tp[l - 1];
       float* Gn;
-      TRY(palloc(f, &Gn, (size_t)B * pl.H * pl.W * cin));
+      TRY(aalloc(f, &Gn, (size_t)B * pl.H * pl.W * cin));
       if (!dry) TRY(maxpool2_bwd_launch(dIn, pl.idx, headG[pt], Gn, B, pl.H, pl.W, cin, st));
       f.ar.free(dIn);
       f.ar.free(headG[pt]);
@@ -155,6 +154,8 @@ int run(hedit_lpips* h, const float* x, const float* src, long src_stride, int B
 
 }  // namespace
 
+HEDIT_LIFECYCLE(lpips, hedit_lpips, "LPIPS", no_pre_destroy)
+
 extern "C" {
 
 int hedit_lpips_create(hedit_lpips** out) try {
@@ -168,38 +169,12 @@ int hedit_lpips_create(hedit_lpips** out) try {
   }
   const int tapc[5] = {64, 128, 256, 512, 512};
   for (int t = 0; t < 5; ++t) h->lin[t] = f32conv(h, "lin" + std::to_string(t) + ".model.1.weight", 1, tapc[t], 1);
-  if (h->alloc_failed) {
-    hedit_set_error("hipMalloc failed while creating the LPIPS network");
-    store_free(h);
-    delete h;
-    return HEDIT_ERR_HIP;
-  }
-  *out = h;
-  return HEDIT_OK;
+  return handle_created(h, out);
 } catch (...) { return hedit_abi_catch(); }
-
-void hedit_lpips_destroy(hedit_lpips* h) try {
-  if (!h) return;
-  store_free(h);
-  delete h;
-} catch (...) { (void)hedit_abi_catch(); }
-
-int hedit_lpips_num_params(const hedit_lpips* h) { return store_num_params(h); }
-const char* hedit_lpips_param_name(const hedit_lpips* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_lpips_param_shape(const hedit_lpips* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
-int hedit_lpips_load(hedit_lpips* h, const char* name, const float* w, size_t numel, void* stream) try {
-  ARG_CHECK(h && name && w, "null");
-  h->finalized = false;
-  return store_load(h, "LPIPS", name, w, numel, reinterpret_cast<hipStream_t>(stream));
-} catch (...) { return hedit_abi_catch(); }
-int hedit_lpips_missing(const hedit_lpips* h) { return h ? store_missing(h) : -1; }
 
 int hedit_lpips_finalize(hedit_lpips* h, void* stream) try {
   ARG_CHECK(h, "null");
-  if (store_missing(h) != 0) {
-    hedit_set_error("LPIPS has " + std::to_string(store_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(handle_loaded(h));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   for (int l = 0; l < VGG_N; ++l) TRY(make_pconv(h, h->conv[l], h->w[l], nullptr, VGG_CH[l][1], VGG_CH[l][0], 3, 0, 0, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -215,8 +190,8 @@ size_t hedit_lpips_workspace_bytes(hedit_lpips* h, int B, int height, int width)
   if (!h || B < 1 || height % 16 || width % 16) return 0;
   size_t peak = 0;
   float dummy = 0.f;
-  if (run(h, nullptr, &dummy, 0, B, height, width, 1.f, nullptr, nullptr, nullptr, nullptr, 0, nullptr, true, true, &peak) != HEDIT_OK) return 0;
-  return peak + 4096;
+  const int rc = run(h, nullptr, &dummy, 0, B, height, width, 1.f, nullptr, nullptr, nullptr, nullptr, 0, nullptr, true, true, &peak);
+  return dry_run_bytes(rc, peak);
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
 /* src fp32 [B][3][H][W] in [-1, 1] -> feats fp32 [B][hedit_lpips_feature_floats(H, W)]: the channel-unit-normalised
@@ -224,7 +199,7 @@ size_t hedit_lpips_workspace_bytes(hedit_lpips* h, int B, int height, int width)
 int hedit_lpips_source(hedit_lpips* h, const float* src, int B, int height, int width, float* feats, void* workspace,
                        size_t workspace_bytes, void* stream) try {
   ARG_CHECK(h && src && feats && workspace && B >= 1 && height % 16 == 0 && width % 16 == 0, "lpips_source args");
-  if (!h->finalized) { hedit_set_error("call hedit_lpips_finalize after loading the parameters"); return HEDIT_ERR_STATE; }
+  TRY(handle_finalized(h));
   return run(h, src, nullptr, 0, B, height, width, 1.f, feats, nullptr, nullptr, workspace, workspace_bytes,
              reinterpret_cast<hipStream_t>(stream), false, false, nullptr);
 } catch (...) { return hedit_abi_catch(); }
@@ -235,7 +210,7 @@ int hedit_lpips_source(hedit_lpips* h, const float* src, int B, int height, int 
 int hedit_lpips_fwd_bwd(hedit_lpips* h, const float* x, const float* src_feats, int src_per_image, int B, int height, int width,
                         float scale, float* loss, float* d_x, void* workspace, size_t workspace_bytes, void* stream) try {
   ARG_CHECK(h && x && src_feats && loss && d_x && workspace && B >= 1 && height % 16 == 0 && width % 16 == 0, "lpips_fwd_bwd args");
-  if (!h->finalized) { hedit_set_error("call hedit_lpips_finalize after loading the parameters"); return HEDIT_ERR_STATE; }
+  TRY(handle_finalized(h));
   return run(h, x, src_feats, src_per_image ? (long)feature_floats(height, width) : 0, B, height, width, scale, nullptr, loss, d_x,
              workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false, true, nullptr);
 } catch (...) { return hedit_abi_catch(); }

@@ -1,8 +1,11 @@
 // Host-side helpers of the "precise" executors (irse.hip, lpips.hip) on the kernels of pnet.hip: operand geometry of the
 // three-term split, packed weights for the forward and the input-gradient GEMM, the fused element-wise -> operand pass and
-// the GEMM call (batch-independent summation order, like every GEMM of the library).  Header-only, like blocks.h.
+// the GEMM call (batch-independent summation order, like every GEMM of the library).  Header-only; the packed weights live in the
+// handle's parameter store (store.h), the activations in an Arena (exec.h).
 #pragma once
-#include "blocks.h"
+#include "exec.h"
+#include "kernels.h"
+#include "store.h"
 
 namespace {
 
@@ -22,16 +25,6 @@ struct PF {
   Arena ar;
   bool dry() const { return ar.dry; }
 };
-
-template <class T>
-int palloc(PF& f, T** out, size_t n) {
-  *out = reinterpret_cast<T*>(f.ar.alloc(n * sizeof(T)));
-  if (!*out) {
-    hedit_set_error("workspace too small (need more than " + std::to_string(f.ar.cap) + " bytes)");
-    return HEDIT_ERR_ARG;
-  }
-  return HEDIT_OK;
-}
 
 int make_pconv(ParamStore* h, PConv& c, const float* w, const float* scale, int O, int I, int k, int perm_hw, int perm_c, hipStream_t st) {
   c.O = O; c.I = I; c.k = k;
@@ -53,7 +46,7 @@ int op_split(PF& f, const float* x, int C, int op, const float* p, const float* 
   s.x = x; s.ldx = C; s.z = z; s.p = p; s.q = q; s.pq_img = pq_img; s.op = op;
   s.Kp = split_kp(C); s.Cs = split_cs(C); s.C = C; s.geo = geo; s.B = f.B; s.H = H; s.W = W;
   const long rows_out = geo == 1 ? rows_in / 4 : (geo == 2 ? rows_in * 4 : rows_in);
-  TRY(palloc(f, out, (size_t)rows_out * s.Kp));
+  TRY(aalloc(f, out, (size_t)rows_out * s.Kp));
   s.out = *out;
   if (!f.dry()) TRY(split3_launch(s, rows_out, f.st));
   return HEDIT_OK;
@@ -70,14 +63,14 @@ int pgemm(PF& f, const bf16_t* A, const PConv& c, bool dgrad, int mode, int Hin,
   p.Hin = Hin; p.Win = Win; p.Cin = Kp;
   p.Hout = mode == 2 ? Hin / 2 : Hin; p.Wout = mode == 2 ? Win / 2 : Win;
   p.ldc = N;
-  TRY(palloc(f, out, (size_t)M * N));
+  TRY(aalloc(f, out, (size_t)M * N));
   p.raw_f32 = *out;
   p.op_bf16 = 1;
   // batch-independent summation order, as everywhere (gemm_canonical_chunk): the batch is in M
   p.chunk_kt = gemm_canonical_chunk((int)(M / f.B) * GEMM_NOMINAL_BATCH, N, p.K);
   const int splits = gemm_plan_splits(p.M, p.N, p.K, p.chunk_kt);
   float* part = nullptr;
-  if (splits > 1) TRY(palloc(f, &part, (size_t)splits * M * N));
+  if (splits > 1) TRY(aalloc(f, &part, (size_t)splits * M * N));
   if (!f.dry()) TRY(gemm_launch(p, splits, part, f.st));
   if (part) f.ar.free(part);
   return HEDIT_OK;

@@ -14,6 +14,7 @@
 // networks is fused (BatchNorm affine, PReLU / ReLU and their gradients, squeeze-excitation scaling,
 // strided sub-sampling, zero-stuffing for the gradient of a stride-2 convolution).
 #include "common.h"
+#include "exec.h"
 #include "kernels.h"
 
 namespace {
@@ -573,28 +574,26 @@ __global__ __launch_bounds__(256) void lpips_reduce_kernel(const float* __restri
 
 }  // namespace
 
-static inline dim3 pgrid(long total) { return dim3(ew_grid(total)); }
-
 int lpips_prep_launch(const float* img, float* out, const float* shift3, const float* scale3, int B, int H, int W, hipStream_t st) {
-  hipLaunchKernelGGL(lpips_prep_kernel, pgrid((long)B * H * W * 3), dim3(256), 0, st, img, out, make_float3(shift3[0], shift3[1], shift3[2]),
+  hipLaunchKernelGGL(lpips_prep_kernel, egrid((long)B * H * W * 3), dim3(256), 0, st, img, out, make_float3(shift3[0], shift3[1], shift3[2]),
                      make_float3(scale3[0], scale3[1], scale3[2]), B, H, W);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }
 int lpips_prep_bwd_launch(const float* g, int ldg, float* dimg, const float* scale3, int B, int H, int W, hipStream_t st) {
-  hipLaunchKernelGGL(lpips_prep_bwd_kernel, pgrid((long)B * 3 * H * W), dim3(256), 0, st, g, ldg, dimg,
+  hipLaunchKernelGGL(lpips_prep_bwd_kernel, egrid((long)B * 3 * H * W), dim3(256), 0, st, g, ldg, dimg,
                      make_float3(scale3[0], scale3[1], scale3[2]), B, H, W);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }
 int maxpool2_launch(const float* z, float* zp, uint8_t* idx, int B, int H, int W, int C, hipStream_t st) {
   ARG_CHECK(H % 2 == 0 && W % 2 == 0, "maxpool2: even size");
-  hipLaunchKernelGGL(maxpool2_kernel, pgrid((long)B * (H / 2) * (W / 2) * C), dim3(256), 0, st, z, zp, idx, B, H, W, C);
+  hipLaunchKernelGGL(maxpool2_kernel, egrid((long)B * (H / 2) * (W / 2) * C), dim3(256), 0, st, z, zp, idx, B, H, W, C);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }
 int maxpool2_bwd_launch(const float* gp, const uint8_t* idx, const float* add, float* G, int B, int H, int W, int C, hipStream_t st) {
-  hipLaunchKernelGGL(maxpool2_bwd_kernel, pgrid((long)B * H * W * C), dim3(256), 0, st, gp, idx, add, G, B, H, W, C);
+  hipLaunchKernelGGL(maxpool2_bwd_kernel, egrid((long)B * H * W * C), dim3(256), 0, st, gp, idx, add, G, B, H, W, C);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }
@@ -617,18 +616,18 @@ int split3_launch(const Split3Params& s, long rows_out, hipStream_t st) {
   ARG_CHECK(s.Kp % 64 == 0 && 3 * s.Cs <= s.Kp + 0 && s.C <= s.Cs, "split3: operand geometry");
   const long total = rows_out * s.Kp;
   if (s.C % 8 == 0 && s.Cs % 8 == 0 && s.ldx % 4 == 0) {
-    hipLaunchKernelGGL(split3_v8_kernel, pgrid(total / 8), dim3(256), 0, st, s, total / 8);
+    hipLaunchKernelGGL(split3_v8_kernel, egrid(total / 8), dim3(256), 0, st, s, total / 8);
     LAUNCH_CHECK();
     return HEDIT_OK;
   }
-  hipLaunchKernelGGL(split3_kernel, pgrid(total), dim3(256), 0, st, s, total);
+  hipLaunchKernelGGL(split3_kernel, egrid(total), dim3(256), 0, st, s, total);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }
 int pack_split3_w_launch(const float* w, const float* scale, bf16_t* out, int O, int I, int k, int dgrad, int Cs, int Kp,
                          int rows_out, int perm_hw, int perm_c, hipStream_t st) {
   const long total = (long)rows_out * k * k * Kp;
-  hipLaunchKernelGGL(pack_split3_w_kernel, pgrid(total), dim3(256), 0, st, w, scale, out, O, I, k * k, dgrad, Cs, Kp, rows_out, perm_hw,
+  hipLaunchKernelGGL(pack_split3_w_kernel, egrid(total), dim3(256), 0, st, w, scale, out, O, I, k * k, dgrad, Cs, Kp, rows_out, perm_hw,
                      perm_c, total);
   LAUNCH_CHECK();
   return HEDIT_OK;
@@ -646,7 +645,7 @@ int bn_fold_bias_launch(const float* bias, const float* g, const float* b, const
   return HEDIT_OK;
 }
 int act_launch(const float* x, const float* p, const float* q, float* y, long total, int C, int op, hipStream_t st) {
-  hipLaunchKernelGGL(act_kernel, pgrid(total), dim3(256), 0, st, x, p, q, y, total, C, op);
+  hipLaunchKernelGGL(act_kernel, egrid(total), dim3(256), 0, st, x, p, q, y, total, C, op);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }
@@ -669,7 +668,7 @@ int se_fc_launch(const float* part, const float* bias, const float* w1, const fl
 }
 int se_combine_launch(const float* u, const float* bias, const float* s, const float* sc, const float* sc_bias, const float* X, int stride,
                       float* Y, int B, int Ho, int Wo, int C, hipStream_t st) {
-  hipLaunchKernelGGL(se_combine_kernel, pgrid((long)B * Ho * Wo * C), dim3(256), 0, st, u, bias, s, sc, sc_bias, X, stride, Y, B, Ho, Wo, C);
+  hipLaunchKernelGGL(se_combine_kernel, egrid((long)B * Ho * Wo * C), dim3(256), 0, st, u, bias, s, sc, sc_bias, X, stride, Y, B, Ho, Wo, C);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }
@@ -688,22 +687,22 @@ int se_fc_bwd_launch(const float* part, const float* sbuf, const float* hbuf, co
 }
 int unit_bwd_combine_launch(const float* dxa, const float* p, const float* dsc, int stride, float* dX, int B, int H, int W, int C,
                             hipStream_t st) {
-  hipLaunchKernelGGL(unit_bwd_combine_kernel, pgrid((long)B * H * W * C), dim3(256), 0, st, dxa, p, dsc, stride, dX, B, H, W, C);
+  hipLaunchKernelGGL(unit_bwd_combine_kernel, egrid((long)B * H * W * C), dim3(256), 0, st, dxa, p, dsc, stride, dX, B, H, W, C);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }
 int scale_cols_launch(const float* x, const float* p, float* y, long total, int n, hipStream_t st) {
-  hipLaunchKernelGGL(scale_cols_kernel, pgrid(total), dim3(256), 0, st, x, p, y, total, n);
+  hipLaunchKernelGGL(scale_cols_kernel, egrid(total), dim3(256), 0, st, x, p, y, total, n);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }
 int face_pool_launch(const float* img, float* out, int B, hipStream_t st) {
-  hipLaunchKernelGGL(face_pool_kernel, pgrid((long)B * 112 * 112 * 3), dim3(256), 0, st, img, out, B);
+  hipLaunchKernelGGL(face_pool_kernel, egrid((long)B * 112 * 112 * 3), dim3(256), 0, st, img, out, B);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }
 int face_pool_bwd_launch(const float* g, int ldg, float* dimg, int B, hipStream_t st) {
-  hipLaunchKernelGGL(face_pool_bwd_kernel, pgrid((long)B * 3 * 256 * 256), dim3(256), 0, st, g, ldg, dimg, B);
+  hipLaunchKernelGGL(face_pool_bwd_kernel, egrid((long)B * 3 * 256 * 256), dim3(256), 0, st, g, ldg, dimg, B);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }

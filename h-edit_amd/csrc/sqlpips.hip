@@ -19,7 +19,9 @@
 // image's arithmetic -- tile partition, K order, block partition of the head, reduction tree -- is a function of (H, W)
 // alone: dist[n] of a batch is bit-identical to the N = 1 call, distance(a, b) to distance(b, a), and distance(a, a) is 0.
 // No float atomics.  Nothing reads the 16-bit storage type: both storage builds give the same bits.
-#include "blocks.h"
+#include "exec.h"
+#include "kernels.h"
+#include "store.h"
 
 namespace {
 
@@ -295,24 +297,14 @@ struct Fire {
 
 }  // namespace
 
-struct hedit_sqlpips : ParamStore {
+struct HEDIT_HANDLE hedit_sqlpips : ParamStore {
   float *w0 = nullptr, *b0 = nullptr;
   Fire fire[NFIRE];
   float* lin[NTAP] = {};
-  bool finalized = false;
 };
 
 namespace {
 
-template <class T>
-int walloc(Arena& ar, T** out, size_t n) {
-  *out = reinterpret_cast<T*>(ar.alloc(n * sizeof(T)));
-  if (!*out) {
-    hedit_set_error("workspace too small (need more than " + std::to_string(ar.cap) + " bytes)");
-    return HEDIT_ERR_ARG;
-  }
-  return HEDIT_OK;
-}
 
 int fire_launch(const Fire& f, const float* x, int imgs, int H, int W, float* out, hipStream_t st) {
   const int tx = cdiv(W, TS), ty = cdiv(H, TS), nt = f.e / 16;
@@ -348,7 +340,7 @@ int run(hedit_sqlpips* h, const float* a, const float* b, int N, int H0, int W0,
     for (int k = 0; k < NTAP; ++k) {
       sa.hw[k] = H * W;
       sa.nblk[k] = cdiv((long)H * W, HEAD_PIX);
-      TRY(walloc(ar, &part[k], (size_t)N * sa.nblk[k]));
+      TRY(aalloc(ar, &part[k], (size_t)N * sa.nblk[k]));
       sa.part[k] = part[k];
       if (k < 3) { H = pool_out(H); W = pool_out(W); }
     }
@@ -362,7 +354,7 @@ int run(hedit_sqlpips* h, const float* a, const float* b, int N, int H0, int W0,
   auto pool = [&](float** cur, int* H, int* W, int C) -> int {
     const int Ho = pool_out(*H), Wo = pool_out(*W);
     float* y;
-    TRY(walloc(ar, &y, (size_t)imgs * Ho * Wo * C));
+    TRY(aalloc(ar, &y, (size_t)imgs * Ho * Wo * C));
     if (!dry) {
       hipLaunchKernelGGL(sq_pool_kernel, dim3(ew_grid((long)imgs * Ho * Wo * C / 4)), dim3(256), 0, st, *cur, y, imgs, *H, *W, Ho, Wo, C);
       LAUNCH_CHECK();
@@ -374,7 +366,7 @@ int run(hedit_sqlpips* h, const float* a, const float* b, int N, int H0, int W0,
   };
   int H = stem_out(H0), W = stem_out(W0);
   float* cur;
-  TRY(walloc(ar, &cur, (size_t)imgs * H * W * 64));
+  TRY(aalloc(ar, &cur, (size_t)imgs * H * W * 64));
   if (!dry) {
     hipLaunchKernelGGL(sq_stem_kernel, dim3(ew_grid((long)imgs * H * W * 4)), dim3(256), 0, st, a, b, N, H0, W0, H, W, h->w0, h->b0, cur);
     LAUNCH_CHECK();
@@ -384,7 +376,7 @@ int run(hedit_sqlpips* h, const float* a, const float* b, int N, int H0, int W0,
   for (int i = 0; i < NFIRE; ++i) {
     const Fire& f = h->fire[i];
     float* y;
-    TRY(walloc(ar, &y, (size_t)imgs * H * W * 2 * f.e));
+    TRY(aalloc(ar, &y, (size_t)imgs * H * W * 2 * f.e));
     if (!dry) TRY(fire_launch(f, cur, imgs, H, W, y, st));
     ar.free(cur);
     cur = y;
@@ -408,6 +400,8 @@ bool sizes_ok(int N, int H, int W) {
 
 }  // namespace
 
+HEDIT_LIFECYCLE(sqlpips, hedit_sqlpips, "SqueezeNet-LPIPS", no_pre_destroy)
+
 extern "C" {
 
 int hedit_sqlpips_create(hedit_sqlpips** out) try {
@@ -428,38 +422,12 @@ int hedit_sqlpips_create(hedit_sqlpips** out) try {
     f.we3p = dalloc<float>(h, (size_t)f.e * f.s * 9);
   }
   for (int k = 0; k < NTAP; ++k) h->lin[k] = f32conv(h, "lin" + std::to_string(k) + ".model.1.weight", 1, TAP_C[k], 1);
-  if (h->alloc_failed) {
-    hedit_set_error("hipMalloc failed while creating the SqueezeNet-LPIPS network");
-    store_free(h);
-    delete h;
-    return HEDIT_ERR_HIP;
-  }
-  *out = h;
-  return HEDIT_OK;
+  return handle_created(h, out);
 } catch (...) { return hedit_abi_catch(); }
-
-void hedit_sqlpips_destroy(hedit_sqlpips* h) try {
-  if (!h) return;
-  store_free(h);
-  delete h;
-} catch (...) { (void)hedit_abi_catch(); }
-
-int hedit_sqlpips_num_params(const hedit_sqlpips* h) { return store_num_params(h); }
-const char* hedit_sqlpips_param_name(const hedit_sqlpips* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_sqlpips_param_shape(const hedit_sqlpips* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
-int hedit_sqlpips_load(hedit_sqlpips* h, const char* name, const float* w, size_t numel, void* stream) try {
-  ARG_CHECK(h && name && w, "null");
-  h->finalized = false;
-  return store_load(h, "SqueezeNet-LPIPS", name, w, numel, reinterpret_cast<hipStream_t>(stream));
-} catch (...) { return hedit_abi_catch(); }
-int hedit_sqlpips_missing(const hedit_sqlpips* h) { return h ? store_missing(h) : -1; }
 
 int hedit_sqlpips_finalize(hedit_sqlpips* h, void* stream) try {
   ARG_CHECK(h, "null");
-  if (store_missing(h) != 0) {
-    hedit_set_error("SqueezeNet-LPIPS has " + std::to_string(store_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(handle_loaded(h));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   for (int i = 0; i < NFIRE; ++i) {
     const Fire& f = h->fire[i];
@@ -474,15 +442,15 @@ int hedit_sqlpips_finalize(hedit_sqlpips* h, void* stream) try {
 size_t hedit_sqlpips_workspace_bytes(hedit_sqlpips* h, int N, int height, int width) try {
   if (!h || !sizes_ok(N, height, width)) return 0;
   size_t peak = 0;
-  if (run(h, nullptr, nullptr, N, height, width, nullptr, nullptr, 0, nullptr, true, &peak) != HEDIT_OK) return 0;
-  return peak + 4096;
+  const int rc = run(h, nullptr, nullptr, N, height, width, nullptr, nullptr, 0, nullptr, true, &peak);
+  return dry_run_bytes(rc, peak);
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
 /* a, b fp32 [N][3][H][W] in [-1, 1] -> dist[n] = LPIPS(a_n, b_n).  Every argument is checked before the first launch. */
 int hedit_sqlpips_distance(hedit_sqlpips* h, const float* a, const float* b, int N, int height, int width, float* dist, void* workspace,
                            size_t workspace_bytes, void* stream) try {
   ARG_CHECK(h && a && b && dist, "sqlpips_distance: null");
-  if (!h->finalized) { hedit_set_error("call hedit_sqlpips_finalize after loading the parameters"); return HEDIT_ERR_STATE; }
+  TRY(handle_finalized(h));
   ARG_CHECK(height >= MIN_SIDE && width >= MIN_SIDE, "sqlpips_distance: height and width must be at least 32");
   ARG_CHECK(height <= MAX_SIDE && width <= MAX_SIDE, "sqlpips_distance: height and width must be at most 4096");
   ARG_CHECK(N >= 1 && N <= HEDIT_SQLPIPS_MAX_BATCH, "sqlpips_distance: 1 <= N <= 64");

@@ -122,12 +122,11 @@ __global__ __launch_bounds__(256) void causal_attn_kernel(const float* __restric
 
 }  // namespace
 
-struct hedit_text : ParamStore {
+struct HEDIT_HANDLE hedit_text : ParamStore {
   hedit_text_cfg cfg;
   float *tok = nullptr, *pos = nullptr, *lnfg = nullptr, *lnfb = nullptr, *proj_w = nullptr;
   PConv proj;
   std::vector<EncBlock> blocks;
-  bool finalized = false;
 };
 
 namespace {
@@ -139,7 +138,7 @@ int run(hedit_text* h, const int32_t* ids, int B, int L, float* hidden, const in
   const long M = (long)B * L;
   const float ascale = 1.0f / sqrtf((float)HD);
   float* T;
-  TRY(palloc(f, &T, (size_t)M * W));
+  TRY(aalloc(f, &T, (size_t)M * W));
   if (!dry) { hipLaunchKernelGGL(embed_kernel, egrid(M * W), dim3(256), 0, st, ids, h->tok, h->pos, T, M, L, W, h->cfg.vocab_size); LAUNCH_CHECK(); }
   auto attn = [&](const float* qkv, const float* bias, float* A) -> int {
     hipLaunchKernelGGL(causal_attn_kernel, dim3(heads, B, attn_slices(heads, B)), dim3(256), attn_lds(L), st, qkv, bias, A, L, W, ascale);
@@ -151,9 +150,9 @@ int run(hedit_text* h, const int32_t* ids, int B, int L, float* hidden, const in
   if (pooled) {
     // the ln_final row at pool_index[b]: gathered before the LayerNorm (a per-row operation, so the bits are those of `hidden`)
     float *R, *N = nullptr, *out;
-    TRY(palloc(f, &R, (size_t)B * W));
+    TRY(aalloc(f, &R, (size_t)B * W));
     if (!dry) TRY(enc_gather_rows_launch(T, pool_index, R, B, L, W, st));
-    if (P > 0) TRY(palloc(f, &N, (size_t)B * W));
+    if (P > 0) TRY(aalloc(f, &N, (size_t)B * W));
     TRY(ln(f, R, h->lnfg, h->lnfb, B, W, LN_EPS, P > 0 ? N : pooled));
     if (P > 0) {
       TRY(lin(f, N, W, P_COPY, nullptr, nullptr, h->proj, true, B, &out));      // one M = B GEMM: x @ text_projection
@@ -169,6 +168,8 @@ int run(hedit_text* h, const int32_t* ids, int B, int L, float* hidden, const in
 }
 
 }  // namespace
+
+HEDIT_LIFECYCLE(text, hedit_text, "text encoder", no_pre_destroy)
 
 extern "C" {
 
@@ -190,38 +191,12 @@ int hedit_text_create(const hedit_text_cfg* cfg, hedit_text** out) try {
   h->lnfg = vec(h, "ln_final.weight", W);
   h->lnfb = vec(h, "ln_final.bias", W);
   if (cfg->proj_dim > 0) h->proj_w = mat(h, "text_projection", W, cfg->proj_dim);
-  if (h->alloc_failed) {
-    hedit_set_error("hipMalloc failed while creating the text encoder");
-    store_free(h);
-    delete h;
-    return HEDIT_ERR_HIP;
-  }
-  *out = h;
-  return HEDIT_OK;
+  return handle_created(h, out);
 } catch (...) { return hedit_abi_catch(); }
-
-void hedit_text_destroy(hedit_text* h) try {
-  if (!h) return;
-  store_free(h);
-  delete h;
-} catch (...) { (void)hedit_abi_catch(); }
-
-int hedit_text_num_params(const hedit_text* h) { return store_num_params(h); }
-const char* hedit_text_param_name(const hedit_text* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_text_param_shape(const hedit_text* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
-int hedit_text_load(hedit_text* h, const char* name, const float* w, size_t numel, void* stream) try {
-  ARG_CHECK(h && name && w, "null");
-  h->finalized = false;
-  return store_load(h, "text encoder", name, w, numel, reinterpret_cast<hipStream_t>(stream));
-} catch (...) { return hedit_abi_catch(); }
-int hedit_text_missing(const hedit_text* h) { return h ? store_missing(h) : -1; }
 
 int hedit_text_finalize(hedit_text* h, void* stream) try {
   ARG_CHECK(h, "null");
-  if (store_missing(h) != 0) {
-    hedit_set_error("text encoder has " + std::to_string(store_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(handle_loaded(h));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int W = h->cfg.width;
   for (EncBlock& k : h->blocks) TRY(enc_pack_block(h, k, W, true, st));
@@ -237,9 +212,8 @@ int hedit_text_finalize(hedit_text* h, void* stream) try {
 size_t hedit_text_workspace_bytes(hedit_text* h, int B, int L) try {
   if (!h || B < 1 || L < 1 || L > h->cfg.context_length) return 0;
   size_t peak = 0;
-  if (run(h, nullptr, B, L, reinterpret_cast<float*>(4096), nullptr, reinterpret_cast<float*>(4096), nullptr, 0, nullptr, true, &peak) != HEDIT_OK)
-    return 0;
-  return peak + 4096;
+  const int rc = run(h, nullptr, B, L, reinterpret_cast<float*>(4096), nullptr, reinterpret_cast<float*>(4096), nullptr, 0, nullptr, true, &peak);
+  return dry_run_bytes(rc, peak);
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
 /* ids int32 [B][L] (device) -> hidden fp32 [B][L][width] after ln_final (or NULL); pooled fp32 [B][proj_dim ? proj_dim : width]
@@ -253,7 +227,7 @@ int hedit_text_encode(hedit_text* h, const int32_t* ids, int B, int L, float* hi
   ARG_CHECK(hidden || pooled, "text_encode: nothing to write (hidden and pooled are both null)");
   ARG_CHECK(!pooled || pool_index, "text_encode: pooled needs pool_index");
   ARG_CHECK(workspace, "text_encode: null workspace");
-  if (!h->finalized) { hedit_set_error("call hedit_text_finalize after loading the parameters"); return HEDIT_ERR_STATE; }
+  TRY(handle_finalized(h));
   size_t need = 0;
   TRY(run(h, nullptr, B, L, hidden, pool_index, pooled, nullptr, 0, nullptr, true, &need));
   TRY(ws_check("text_encode", need, workspace_bytes));

@@ -10,40 +10,11 @@
 #include <string>
 #include <vector>
 
-#include "../../include/hedit.h"
-#include "common.h"
 #include "exec.h"
 #include "kernels.h"
-
-#define TRY(expr)                        \
-  do {                                   \
-    int _rc = (expr);                    \
-    if (_rc != HEDIT_OK) return _rc;     \
-  } while (0)
+#include "store.h"
 
 namespace {
-
-struct Slot {
-  std::string name;
-  int kind;        // 0 fp32 copy, 1 linear -> bf16 (scaled), 2 conv3x3 OIHW -> bf16 [O][9][I],
-                   // 3 / 4: FF1 weight / bias with GEGLU (value16|gate16) row interleave,
-                   // 5: layer `which` of the block-tail weight stream (ffn.hip), 6: the FF1 bias in that kernel's packed
-                   // order, 7: layer `which` of a projection-chain weight stream of `lay` layers (linchain.hip)
-  void* dst;
-  size_t numel;
-  int O, I;
-  float scale;
-  bool loaded;
-  int ndim;
-  int dims[4];
-  int which = 0, lay = 0;
-  // hedit_unet_create_grad: further destinations the same checkpoint tensor is packed into (the input-gradient twins, and at
-  // the chain width the unfused forward weights).  kind: 0 fp32 copy, 1 linear -> bf16 (scaled), 10 linear [O][I] -> bf16 [I][O]
-  // (scaled), 11 conv3x3 -> bf16 [I][9][O] taps flipped, 12 the same with the taps in place (stride-2 dgrad), 13 OIHW -> fp32
-  // IOHW taps flipped
-  struct Extra { int kind; void* dst; float scale; int O, I; long ld = 0; };      // ld: row stride of a kind-10 destination (0 = dense)
-  std::vector<Extra> extra;
-};
 
 struct Res {
   int cin, cout, temb_off;
@@ -81,11 +52,8 @@ struct Block {
 
 }  // namespace
 
-struct hedit_unet {
+struct HEDIT_HANDLE hedit_unet : ParamStore {
   hedit_unet_cfg cfg;
-  std::vector<void*> owned;
-  std::vector<Slot> slots;
-  std::map<std::string, int> index;
   int temb_dim = 0, temb_total = 0;
   // stem / head
   float *conv_in_w = nullptr, *conv_in_b = nullptr, *te1_b = nullptr, *te2_b = nullptr;
@@ -128,76 +96,33 @@ struct hedit_unet {
 
 namespace {
 
-template <class T>
-T* dalloc(hedit_unet* h, size_t n) {
-  void* p = nullptr;
-  if (hipMalloc(&p, n * sizeof(T) > 0 ? n * sizeof(T) : 16) != hipSuccess) return nullptr;
-  h->owned.push_back(p);
-  return reinterpret_cast<T*>(p);
-}
-
-void add_slot(hedit_unet* h, const std::string& name, int kind, void* dst, size_t numel, int O = 0, int I = 0, float scale = 1.f) {
-  Slot s{name, kind, dst, numel, O, I, scale, false, 1, {(int)numel, 1, 1, 1}};
-  if (kind == 1) { s.ndim = 2; s.dims[0] = O; s.dims[1] = I; }
-  if (kind == 2) { s.ndim = 4; s.dims[0] = O; s.dims[1] = I; s.dims[2] = 3; s.dims[3] = 3; }
-  // 1x1 convolutions keep their 4-D torch shape
-  if (kind == 1 && (name.find("proj_in.weight") != std::string::npos || name.find("proj_out.weight") != std::string::npos ||
-                    name.find("conv_shortcut.weight") != std::string::npos)) {
-    s.ndim = 4; s.dims[2] = 1; s.dims[3] = 1;
-  }
-  h->index[name] = (int)h->slots.size();
-  h->slots.push_back(s);
-}
-float* f32p(hedit_unet* h, const std::string& name, size_t n, float* dst = nullptr) {
-  if (!dst) dst = dalloc<float>(h, n);
-  add_slot(h, name, 0, dst, n);
-  return dst;
-}
-bf16_t* linp(hedit_unet* h, const std::string& name, int O, int I, bf16_t* dst = nullptr, float scale = 1.f) {
-  if (!dst) dst = dalloc<bf16_t>(h, (size_t)O * I);
-  add_slot(h, name, 1, dst, (size_t)O * I, O, I, scale);
-  return dst;
-}
-bf16_t* conv3p(hedit_unet* h, const std::string& name, int O, int I) {
-  bf16_t* dst = dalloc<bf16_t>(h, (size_t)O * I * 9);
-  add_slot(h, name, 2, dst, (size_t)O * I * 9, O, I);
-  return dst;
-}
-
-// grad handle: one more destination for the slot just added
-template <class T>
-T* add_extra(hedit_unet* h, int kind, T* dst, size_t n, int O, int I, float scale = 1.f) {
-  if (!dst) dst = dalloc<T>(h, n);
-  h->slots.back().extra.push_back({kind, dst, scale, O, I});
-  return dst;
-}
 // grad handle: the linear slot just added also fills its transposed twin *t and, where the forward-only handle keeps the
 // weight in a chain stream only (fwd != nullptr), the unfused forward copy *fwd (allocated here unless it is set)
 void grad_lin(hedit_unet* h, int O, int I, float scale, bf16_t** t, bf16_t** fwd = nullptr) {
   if (!h->grad) return;
-  *t = add_extra<bf16_t>(h, 10, nullptr, (size_t)O * I, O, I, scale);
-  if (fwd) *fwd = add_extra<bf16_t>(h, 1, *fwd, (size_t)O * I, O, I, scale);
+  *t = twin<bf16_t>(h, Pack::LinearT, (size_t)O * I, nullptr, scale);
+  if (fwd) *fwd = twin<bf16_t>(h, Pack::Linear, (size_t)O * I, *fwd, scale);
 }
 
 Res make_res(hedit_unet* h, const std::string& pre, int cin, int cout, int& temb_off) {
   Res r{};
   r.cin = cin; r.cout = cout; r.temb_off = temb_off;
-  r.n1g = f32p(h, pre + ".norm1.weight", cin);
-  r.n1b = f32p(h, pre + ".norm1.bias", cin);
-  r.conv1 = conv3p(h, pre + ".conv1.weight", cout, cin);
-  if (h->grad) r.conv1_t = add_extra<bf16_t>(h, 11, nullptr, (size_t)cout * cin * 9, cout, cin);
-  f32p(h, pre + ".conv1.bias", cout, h->conv1_b_all + temb_off);
-  linp(h, pre + ".time_emb_proj.weight", cout, h->temb_dim, h->temb_w_all + (size_t)temb_off * h->temb_dim);
-  f32p(h, pre + ".time_emb_proj.bias", cout, h->temb_b_all + temb_off);
-  r.n2g = f32p(h, pre + ".norm2.weight", cout);
-  r.n2b = f32p(h, pre + ".norm2.bias", cout);
-  r.conv2 = conv3p(h, pre + ".conv2.weight", cout, cout);
-  if (h->grad) r.conv2_t = add_extra<bf16_t>(h, 11, nullptr, (size_t)cout * cout * 9, cout, cout);
-  r.conv2_b = f32p(h, pre + ".conv2.bias", cout);
+  r.n1g = vec(h, pre + ".norm1.weight", cin);
+  r.n1b = vec(h, pre + ".norm1.bias", cin);
+  r.conv1 = conv3(h, pre + ".conv1.weight", cout, cin);
+  if (h->grad) r.conv1_t = twin<bf16_t>(h, Pack::Conv3Dgrad, (size_t)cout * cin * 9);
+  vec(h, pre + ".conv1.bias", cout, h->conv1_b_all + temb_off);
+  lin(h, pre + ".time_emb_proj.weight", cout, h->temb_dim, false, h->temb_w_all + (size_t)temb_off * h->temb_dim);
+  vec(h, pre + ".time_emb_proj.bias", cout, h->temb_b_all + temb_off);
+  r.n2g = vec(h, pre + ".norm2.weight", cout);
+  r.n2b = vec(h, pre + ".norm2.bias", cout);
+  r.conv2 = conv3(h, pre + ".conv2.weight", cout, cout);
+  if (h->grad) r.conv2_t = twin<bf16_t>(h, Pack::Conv3Dgrad, (size_t)cout * cout * 9);
+  r.conv2_b = vec(h, pre + ".conv2.bias", cout);
   if (cin != cout) {
-    r.sc_w = linp(h, pre + ".conv_shortcut.weight", cout, cin);
+    r.sc_w = lin(h, pre + ".conv_shortcut.weight", cout, cin, true);
     grad_lin(h, cout, cin, 1.f, &r.sc_t);
-    r.sc_b = f32p(h, pre + ".conv_shortcut.bias", cout);
+    r.sc_b = vec(h, pre + ".conv_shortcut.bias", cout);
   }
   temb_off += cout;
   return r;
@@ -209,18 +134,16 @@ Attn make_attn(hedit_unet* h, const std::string& pre, int C) {
   const int ctx = h->cfg.cross_attention_dim;
   const int d = C / h->cfg.heads;
   const float qscale = 1.0f / sqrtf((float)d) * 1.4426950408889634f;   // softmax scale * log2(e)
-  a.gn_g = f32p(h, pre + ".norm.weight", C);
-  a.gn_b = f32p(h, pre + ".norm.bias", C);
+  a.gn_g = vec(h, pre + ".norm.weight", C);
+  a.gn_b = vec(h, pre + ".norm.bias", C);
   // At the level ffn.hip / linchain.hip exist for, the token-local layers of the block run as three kernels -- GroupNorm apply +
   // proj_in + norm1 + q | k | v^T;  attn1.to_out + residual + norm2 + attn2.to_q;  attn2.to_out + residual + norm3 +
-  // feed-forward + proj_out + residual -- and their weights go into those kernels' streams (slot kind 5), the FF1 bias
-  // into its packed form (kind 6); none of them is kept as a GEMM operand.
+  // feed-forward + proj_out + residual -- and their weights go into those kernels' streams (Pack::ChainLayer / FfnLayer), the FF1
+  // bias into its packed form (Pack::FfnBias); none of them is kept as a GEMM operand.
   const bool chain = C == ffn_fused_channels();
   auto stream_slot = [&](const std::string& name, bf16_t* stream, int lay, int which, int O, int I, float scale, int ndim) {
-    add_slot(h, name, lay ? 7 : 5, stream, (size_t)O * I, O, I, scale);
-    Slot& sl = h->slots.back();
-    sl.which = which; sl.lay = lay; sl.ndim = ndim;
-    sl.dims[0] = O; sl.dims[1] = I; sl.dims[2] = 1; sl.dims[3] = 1;
+    PackDst& d = add_slot(h, name, lay ? Pack::ChainLayer : Pack::FfnLayer, stream, (size_t)O * I, O, I, ndim, O, I, 1, 1).to;
+    d.scale = scale; d.which = which; d.lay = lay;
   };
   const std::string tb = pre + ".transformer_blocks.0";
   if (chain) {
@@ -230,12 +153,12 @@ Attn make_attn(hedit_unet* h, const std::string& pre, int C) {
     a.ff1_bp = dalloc<float>(h, ffn_bias_bytes() / sizeof(float));
     stream_slot(pre + ".proj_in.weight", a.frs, 4, 0, C, C, 1.f, 4);
   } else {
-    a.pin = linp(h, pre + ".proj_in.weight", C, C);
+    a.pin = lin(h, pre + ".proj_in.weight", C, C, true);
   }
   grad_lin(h, C, C, 1.f, &a.pin_t, chain ? &a.pin : nullptr);
-  a.pin_b = f32p(h, pre + ".proj_in.bias", C);
-  a.ln1g = f32p(h, tb + ".norm1.weight", C);
-  a.ln1b = f32p(h, tb + ".norm1.bias", C);
+  a.pin_b = vec(h, pre + ".proj_in.bias", C);
+  a.ln1g = vec(h, tb + ".norm1.weight", C);
+  a.ln1b = vec(h, tb + ".norm1.bias", C);
   if (chain) {
     bf16_t *wq = nullptr, *wk = nullptr;
     if (h->grad) {
@@ -253,67 +176,61 @@ Attn make_attn(hedit_unet* h, const std::string& pre, int C) {
     grad_lin(h, C, C, 1.f, &a.wo1_t, &a.w_o1);
   } else {
     a.w_qk = dalloc<bf16_t>(h, (size_t)2 * C * C);
-    linp(h, tb + ".attn1.to_q.weight", C, C, a.w_qk, qscale);
+    lin(h, tb + ".attn1.to_q.weight", C, C, false, a.w_qk, qscale);
     grad_lin(h, C, C, qscale, &a.wq1_t);
-    linp(h, tb + ".attn1.to_k.weight", C, C, a.w_qk + (size_t)C * C);
+    lin(h, tb + ".attn1.to_k.weight", C, C, false, a.w_qk + (size_t)C * C);
     grad_lin(h, C, C, 1.f, &a.wk1_t);
-    a.w_v1 = linp(h, tb + ".attn1.to_v.weight", C, C);
+    a.w_v1 = lin(h, tb + ".attn1.to_v.weight", C, C);
     grad_lin(h, C, C, 1.f, &a.wv1_t);
-    a.w_o1 = linp(h, tb + ".attn1.to_out.0.weight", C, C);
+    a.w_o1 = lin(h, tb + ".attn1.to_out.0.weight", C, C);
     grad_lin(h, C, C, 1.f, &a.wo1_t);
   }
-  a.o1_b = f32p(h, tb + ".attn1.to_out.0.bias", C);
-  a.ln2g = f32p(h, tb + ".norm2.weight", C);
-  a.ln2b = f32p(h, tb + ".norm2.bias", C);
+  a.o1_b = vec(h, tb + ".attn1.to_out.0.bias", C);
+  a.ln2g = vec(h, tb + ".norm2.weight", C);
+  a.ln2b = vec(h, tb + ".norm2.bias", C);
   if (chain) stream_slot(tb + ".attn2.to_q.weight", a.k1s, 2, 1, C, C, qscale, 2);
-  else a.w_q2 = linp(h, tb + ".attn2.to_q.weight", C, C, nullptr, qscale);
+  else a.w_q2 = lin(h, tb + ".attn2.to_q.weight", C, C, false, nullptr, qscale);
   grad_lin(h, C, C, qscale, &a.wq2_t, chain ? &a.w_q2 : nullptr);
   a.ctx_off = h->ctx_next;
   h->ctx_next += C;
-  a.w_k2 = linp(h, tb + ".attn2.to_k.weight", C, ctx, h->wk2_all + (size_t)a.ctx_off * ctx);
-  if (h->wkv2_t) {
-    add_extra<bf16_t>(h, 10, h->wkv2_t + a.ctx_off, (size_t)C * ctx, C, ctx);
-    h->slots.back().extra.back().ld = 2L * h->ctx_n;
-  }
-  a.w_v2 = linp(h, tb + ".attn2.to_v.weight", C, ctx, h->wv2_all + (size_t)a.ctx_off * ctx);
-  if (h->wkv2_t) {
-    add_extra<bf16_t>(h, 10, h->wkv2_t + h->ctx_n + a.ctx_off, (size_t)C * ctx, C, ctx);
-    h->slots.back().extra.back().ld = 2L * h->ctx_n;
-  }
+  a.w_k2 = lin(h, tb + ".attn2.to_k.weight", C, ctx, false, h->wk2_all + (size_t)a.ctx_off * ctx);
+  if (h->wkv2_t) twin<bf16_t>(h, Pack::LinearT, (size_t)C * ctx, h->wkv2_t + a.ctx_off, 1.f, 2L * h->ctx_n);
+  a.w_v2 = lin(h, tb + ".attn2.to_v.weight", C, ctx, false, h->wv2_all + (size_t)a.ctx_off * ctx);
+  if (h->wkv2_t) twin<bf16_t>(h, Pack::LinearT, (size_t)C * ctx, h->wkv2_t + h->ctx_n + a.ctx_off, 1.f, 2L * h->ctx_n);
   if (chain) {
     stream_slot(tb + ".attn2.to_out.0.weight", a.ffs, 0, 0, C, C, 1.f, 2);
   } else {
-    a.w_o2 = linp(h, tb + ".attn2.to_out.0.weight", C, C);
+    a.w_o2 = lin(h, tb + ".attn2.to_out.0.weight", C, C);
   }
   grad_lin(h, C, C, 1.f, &a.wo2_t, chain ? &a.w_o2 : nullptr);
-  a.o2_b = f32p(h, tb + ".attn2.to_out.0.bias", C);
-  a.ln3g = f32p(h, tb + ".norm3.weight", C);
-  a.ln3b = f32p(h, tb + ".norm3.bias", C);
+  a.o2_b = vec(h, tb + ".attn2.to_out.0.bias", C);
+  a.ln3g = vec(h, tb + ".norm3.weight", C);
+  a.ln3b = vec(h, tb + ".norm3.bias", C);
   if (chain) {
     stream_slot(tb + ".ff.net.0.proj.weight", a.ffs, 0, 1, 8 * C, C, 1.f, 2);
     grad_lin(h, 8 * C, C, 1.f, &a.ff1_t, &a.ff1n);
-    add_slot(h, tb + ".ff.net.0.proj.bias", 6, a.ff1_bp, (size_t)8 * C);
-    if (h->grad) a.ff1_bn = add_extra<float>(h, 0, nullptr, (size_t)8 * C, 0, 0);
+    add_slot(h, tb + ".ff.net.0.proj.bias", Pack::FfnBias, a.ff1_bp, (size_t)8 * C, 0, 0, 1, 8 * C, 1, 1, 1);
+    if (h->grad) a.ff1_bn = twin<float>(h, Pack::F32, (size_t)8 * C);
     stream_slot(tb + ".ff.net.2.weight", a.ffs, 0, 2, C, 4 * C, 1.f, 2);
     grad_lin(h, C, 4 * C, 1.f, &a.ff2_t, &a.ff2);
   } else {
-    a.ff1 = linp(h, tb + ".ff.net.0.proj.weight", 8 * C, C);
-    h->slots.back().kind = 3;
+    a.ff1 = lin(h, tb + ".ff.net.0.proj.weight", 8 * C, C);
+    h->slots.back().to.kind = Pack::GegluRows;
     grad_lin(h, 8 * C, C, 1.f, &a.ff1_t, &a.ff1n);
-    a.ff1_b = f32p(h, tb + ".ff.net.0.proj.bias", 8 * C);
-    h->slots.back().kind = 4;
-    if (h->grad) a.ff1_bn = add_extra<float>(h, 0, nullptr, (size_t)8 * C, 0, 0);
-    a.ff2 = linp(h, tb + ".ff.net.2.weight", C, 4 * C);
+    a.ff1_b = vec(h, tb + ".ff.net.0.proj.bias", 8 * C);
+    h->slots.back().to.kind = Pack::GegluBias;
+    if (h->grad) a.ff1_bn = twin<float>(h, Pack::F32, (size_t)8 * C);
+    a.ff2 = lin(h, tb + ".ff.net.2.weight", C, 4 * C);
     grad_lin(h, C, 4 * C, 1.f, &a.ff2_t);
   }
-  a.ff2_b = f32p(h, tb + ".ff.net.2.bias", C);
+  a.ff2_b = vec(h, tb + ".ff.net.2.bias", C);
   if (chain) {
     stream_slot(pre + ".proj_out.weight", a.ffs, 0, 3, C, C, 1.f, 4);
   } else {
-    a.pout = linp(h, pre + ".proj_out.weight", C, C);
+    a.pout = lin(h, pre + ".proj_out.weight", C, C, true);
   }
   grad_lin(h, C, C, 1.f, &a.pout_t, chain ? &a.pout : nullptr);
-  a.pout_b = f32p(h, pre + ".proj_out.bias", C);
+  a.pout_b = vec(h, pre + ".proj_out.bias", C);
   return a;
 }
 
@@ -349,11 +266,6 @@ struct BatchScope {
   BatchScope& operator=(const BatchScope&) = delete;
 };
 
-#define RUN(f, expr)            \
-  do {                          \
-    if (!(f).dry()) TRY(expr);  \
-  } while (0)
-
 // kernel classes of the sampled profiler
 enum { PK_CONV = 0, PK_LINEAR = 1, PK_SELF_ATTN = 2, PK_CROSS_ATTN = 3, PK_NORM = 4, PK_OTHER = 5, PK_COUNT = 6 };
 
@@ -376,16 +288,6 @@ ProfScope::ProfScope(Fwd& f, int kind, double flops, double bytes) : h(f.h), st(
   h->prof_recs.push_back(r);
   rec = (int)h->prof_recs.size() - 1;
   (void)hipEventRecord(h->prof_pool[r.e0], st);
-}
-
-template <class T>
-int aalloc(Fwd& f, T** out, size_t n) {
-  *out = reinterpret_cast<T*>(f.ar.alloc(n * sizeof(T)));
-  if (!*out) {
-    hedit_set_error("workspace too small (need more than " + std::to_string(f.ar.cap) + " bytes)");
-    return HEDIT_ERR_ARG;
-  }
-  return HEDIT_OK;
 }
 
 // batch_in: which extent of the GEMM carries the batch (1 = M, 2 = N, 0 = neither).  The K-chunking is taken from
@@ -979,6 +881,12 @@ int forward_impl(hedit_unet* h, const float* x, float t, const float* ctx, int B
 
 #include "unetgrad.h"
 
+static void unet_pre_destroy(hedit_unet* h) {
+  drop_tape(h);
+  for (hipEvent_t e : h->prof_pool) (void)hipEventDestroy(e);
+}
+HEDIT_LIFECYCLE(unet, hedit_unet, "", unet_pre_destroy)
+
 // =============================================================================== C ABI
 // grad: attach the input-gradient twins (hedit_unet_create_grad); without it, exactly the forward-only handle
 // ctx: also the transposed context projections (hedit_unet_create_grad_ctx)
@@ -1015,20 +923,16 @@ static int create_impl(const hedit_unet_cfg* cfg, hedit_unet** out, bool grad, b
   h->temb_b_all = dalloc<float>(h, total);
   h->conv1_b_all = dalloc<float>(h, total);
 
-  h->conv_in_w = f32p(h, "conv_in.weight", (size_t)ch[0] * cfg->in_channels * 9);
-  {
-    Slot& cs = h->slots.back();
-    cs.ndim = 4; cs.dims[0] = ch[0]; cs.dims[1] = cfg->in_channels; cs.dims[2] = 3; cs.dims[3] = 3;
-  }
+  h->conv_in_w = f32conv(h, "conv_in.weight", ch[0], cfg->in_channels, 3);
   if (grad) {   // [4][9][ch0], rows beyond in_channels zero: the N = 4 route of the head convolution
-    h->conv_in_t = add_extra<bf16_t>(h, 11, nullptr, (size_t)4 * 9 * ch[0], ch[0], cfg->in_channels);
-    if (h->conv_in_t && hipMemset(h->conv_in_t, 0, (size_t)4 * 9 * ch[0] * sizeof(bf16_t)) != hipSuccess) h->conv_in_t = nullptr;
+    h->conv_in_t = twin<bf16_t>(h, Pack::Conv3Dgrad, (size_t)4 * 9 * ch[0]);
+    if (h->conv_in_t && hipMemset(h->conv_in_t, 0, (size_t)4 * 9 * ch[0] * sizeof(bf16_t)) != hipSuccess) h->alloc_failed = true;
   }
-  h->conv_in_b = f32p(h, "conv_in.bias", ch[0]);
-  h->te1_w = linp(h, "time_embedding.linear_1.weight", h->temb_dim, ch[0]);
-  h->te1_b = f32p(h, "time_embedding.linear_1.bias", h->temb_dim);
-  h->te2_w = linp(h, "time_embedding.linear_2.weight", h->temb_dim, h->temb_dim);
-  h->te2_b = f32p(h, "time_embedding.linear_2.bias", h->temb_dim);
+  h->conv_in_b = vec(h, "conv_in.bias", ch[0]);
+  h->te1_w = lin(h, "time_embedding.linear_1.weight", h->temb_dim, ch[0]);
+  h->te1_b = vec(h, "time_embedding.linear_1.bias", h->temb_dim);
+  h->te2_w = lin(h, "time_embedding.linear_2.weight", h->temb_dim, h->temb_dim);
+  h->te2_b = vec(h, "time_embedding.linear_2.bias", h->temb_dim);
 
   for (int i = 0; i < n; ++i) {
     if (cfg->down_has_attn[i]) h->ctx_n += L * ch[i];
@@ -1054,9 +958,9 @@ static int create_impl(const hedit_unet_cfg* cfg, hedit_unet** out, bool grad, b
     }
     if (i != n - 1) {
       b.has_sampler = true;
-      b.samp_w = conv3p(h, pre + ".downsamplers.0.conv.weight", outc, outc);
-      if (grad) b.samp_t = add_extra<bf16_t>(h, 12, nullptr, (size_t)outc * outc * 9, outc, outc);
-      b.samp_b = f32p(h, pre + ".downsamplers.0.conv.bias", outc);
+      b.samp_w = conv3(h, pre + ".downsamplers.0.conv.weight", outc, outc);
+      if (grad) b.samp_t = twin<bf16_t>(h, Pack::Conv3S2Dgrad, (size_t)outc * outc * 9);
+      b.samp_b = vec(h, pre + ".downsamplers.0.conv.bias", outc);
     }
     h->down.push_back(b);
   }
@@ -1080,21 +984,21 @@ static int create_impl(const hedit_unet_cfg* cfg, hedit_unet** out, bool grad, b
     }
     if (i != n - 1) {
       b.has_sampler = true;
-      b.samp_w = conv3p(h, pre + ".upsamplers.0.conv.weight", outc, outc);
-      if (grad) b.samp_t = add_extra<bf16_t>(h, 11, nullptr, (size_t)outc * outc * 9, outc, outc);
-      b.samp_b = f32p(h, pre + ".upsamplers.0.conv.bias", outc);
+      b.samp_w = conv3(h, pre + ".upsamplers.0.conv.weight", outc, outc);
+      if (grad) b.samp_t = twin<bf16_t>(h, Pack::Conv3Dgrad, (size_t)outc * outc * 9);
+      b.samp_b = vec(h, pre + ".upsamplers.0.conv.bias", outc);
     }
     h->up.push_back(b);
   }
-  h->gn_out_g = f32p(h, "conv_norm_out.weight", ch[0]);
-  h->gn_out_b = f32p(h, "conv_norm_out.bias", ch[0]);
-  h->conv_out_w = conv3p(h, "conv_out.weight", cfg->out_channels, ch[0]);
+  h->gn_out_g = vec(h, "conv_norm_out.weight", ch[0]);
+  h->gn_out_b = vec(h, "conv_norm_out.bias", ch[0]);
+  h->conv_out_w = conv3(h, "conv_out.weight", cfg->out_channels, ch[0]);
   if (grad) {
-    h->conv_out_t = add_extra<float>(h, 13, nullptr, (size_t)cfg->out_channels * ch[0] * 9, cfg->out_channels, ch[0]);
+    h->conv_out_t = twin<float>(h, Pack::FlipOIHW, (size_t)cfg->out_channels * ch[0] * 9);
     h->zero_bias = dalloc<float>(h, ch[0]);
-    if (h->zero_bias && hipMemset(h->zero_bias, 0, ch[0] * sizeof(float)) != hipSuccess) h->zero_bias = nullptr;
+    if (h->zero_bias && hipMemset(h->zero_bias, 0, ch[0] * sizeof(float)) != hipSuccess) h->alloc_failed = true;
   }
-  h->conv_out_b = f32p(h, "conv_out.bias", cfg->out_channels);
+  h->conv_out_b = vec(h, "conv_out.bias", cfg->out_channels);
 
   {
     // identity row list for "all rows are singles" (controller off), sized once: nothing is allocated or copied
@@ -1103,29 +1007,16 @@ static int create_impl(const hedit_unet_cfg* cfg, hedit_unet** out, bool grad, b
     std::vector<int32_t> v(IOTA);
     for (int i = 0; i < IOTA; ++i) v[i] = i;
     h->iota = dalloc<int32_t>(h, IOTA);
-    if (h->iota && hipMemcpy(h->iota, v.data(), IOTA * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) h->iota = nullptr;
-    h->iota_cap = h->iota ? IOTA : 0;
+    if (h->iota && hipMemcpy(h->iota, v.data(), IOTA * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) h->alloc_failed = true;
+    h->iota_cap = IOTA;
   }
-  if (h->ctx_next != h->ctx_n) {      // every block must have taken exactly its slice of the stacked attn2.to_k / to_v matrices
-    hedit_set_error("internal: stacked context-projection plan mismatch");
-    delete h;
+  // every block must have taken exactly its slice of the stacked attn2.to_k / to_v matrices and of the time-embedding projection
+  if (h->ctx_next != h->ctx_n || toff != total) {
+    hedit_set_error(h->ctx_next != h->ctx_n ? "internal: stacked context-projection plan mismatch" : "internal: time-embedding plan mismatch");
+    hedit_unet_destroy(h);
     return HEDIT_ERR_STATE;
   }
-  if (toff != total) {
-    hedit_set_error("internal: time-embedding plan mismatch");
-    delete h;
-    return HEDIT_ERR_STATE;
-  }
-  if (ctx && !h->wkv2_t) { hedit_set_error("hipMalloc failed for the transposed context projections"); return HEDIT_ERR_HIP; }
-  for (void* p : h->owned)
-    if (!p) { hedit_set_error("hipMalloc failed while creating the UNet"); return HEDIT_ERR_HIP; }
-  for (auto& s : h->slots) {
-    if (!s.dst) { hedit_set_error("hipMalloc failed for " + s.name); return HEDIT_ERR_HIP; }
-    for (auto& e : s.extra)
-      if (!e.dst) { hedit_set_error("hipMalloc failed for the gradient twin of " + s.name); return HEDIT_ERR_HIP; }
-  }
-  *out = h;
-  return HEDIT_OK;
+  return handle_created(h, out);
 }
 
 extern "C" {
@@ -1142,84 +1033,11 @@ int hedit_unet_create_grad_ctx(const hedit_unet_cfg* cfg, hedit_unet** out) try 
   return create_impl(cfg, out, true, true);
 } catch (...) { return hedit_abi_catch(); }
 
-void hedit_unet_destroy(hedit_unet* h) try {
-  if (!h) return;
-  drop_tape(h);
-  for (void* p : h->owned) (void)hipFree(p);
-  for (hipEvent_t e : h->prof_pool) (void)hipEventDestroy(e);
-  delete h;
-} catch (...) { (void)hedit_abi_catch(); }
-
-int hedit_unet_num_params(const hedit_unet* h) { return h ? (int)h->slots.size() : 0; }
-const char* hedit_unet_param_name(const hedit_unet* h, int i) try {
-  if (!h || i < 0 || i >= (int)h->slots.size()) return nullptr;
-  return h->slots[i].name.c_str();
-} catch (...) { (void)hedit_abi_catch(); return nullptr; }
-
-int hedit_unet_param_shape(const hedit_unet* h, int i, int* ndim, int* dims4) try {
-  ARG_CHECK(h && ndim && dims4 && i >= 0 && i < (int)h->slots.size(), "param index");
-  *ndim = h->slots[i].ndim;
-  for (int k = 0; k < 4; ++k) dims4[k] = h->slots[i].dims[k];
-  return HEDIT_OK;
-} catch (...) { return hedit_abi_catch(); }
-
 /* 1: the executor keeps this parameter as an unscaled bf16 copy (matrices, convolutions), so handing it over rounded to
    bf16 loses nothing -- what the start-up weight broadcast uses to halve its blob; 0: kept in fp32 or scaled while packed */
 int hedit_unet_param_bf16_exact(const hedit_unet* h, int i) try {
-  if (!h || i < 0 || i >= (int)h->slots.size()) return 0;
-  const Slot& s = h->slots[i];
-  return (((s.kind == 1 || s.kind == 7) && s.scale == 1.f) || s.kind == 2 || s.kind == 3 || s.kind == 5) ? 1 : 0;
+  return store_param_bf16_exact(h, i);
 } catch (...) { (void)hedit_abi_catch(); return 0; }
-
-int hedit_unet_load(hedit_unet* h, const char* name, const float* w, size_t numel, void* stream) try {
-  ARG_CHECK(h && name && w, "null");
-  auto it = h->index.find(name);
-  if (it == h->index.end()) {
-    hedit_set_error(std::string("unknown parameter: ") + name);
-    return HEDIT_ERR_ARG;
-  }
-  Slot& s = h->slots[it->second];
-  if (s.numel != numel) {
-    hedit_set_error(std::string("size mismatch for ") + name + ": expected " + std::to_string(s.numel) + ", got " + std::to_string(numel));
-    return HEDIT_ERR_ARG;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (s.kind == 0) {
-    HIP_TRY(hipMemcpyAsync(s.dst, w, numel * sizeof(float), hipMemcpyDeviceToDevice, st));
-  } else if (s.kind == 1) {
-    TRY(pack_linear_launch(w, reinterpret_cast<bf16_t*>(s.dst), (long)numel, s.scale, st));
-  } else if (s.kind == 3) {
-    TRY(pack_geglu_rows_launch(w, reinterpret_cast<bf16_t*>(s.dst), nullptr, s.O, s.I, st));
-  } else if (s.kind == 4) {
-    TRY(pack_geglu_rows_launch(w, nullptr, reinterpret_cast<float*>(s.dst), (int)numel, 1, st));
-  } else if (s.kind == 5) {
-    TRY(ffn_pack_launch(w, s.which, 1, 1, reinterpret_cast<bf16_t*>(s.dst), st));
-  } else if (s.kind == 6) {
-    TRY(ffn_pack_bias_launch(w, reinterpret_cast<float*>(s.dst), st));
-  } else if (s.kind == 7) {
-    TRY(lin_chain_pack_launch(w, s.which, s.scale, s.lay, reinterpret_cast<bf16_t*>(s.dst), st));
-  } else {
-    TRY(pack_conv3x3_launch(w, reinterpret_cast<bf16_t*>(s.dst), s.O, s.I, st));
-  }
-  for (const Slot::Extra& e : s.extra) {
-    bf16_t* d16 = reinterpret_cast<bf16_t*>(e.dst);
-    if (e.kind == 0) HIP_TRY(hipMemcpyAsync(e.dst, w, numel * sizeof(float), hipMemcpyDeviceToDevice, st));
-    else if (e.kind == 1) TRY(pack_linear_launch(w, d16, (long)numel, e.scale, st));
-    else if (e.kind == 10) TRY(pack_linear_t_launch(w, d16, e.O, e.I, st, e.scale, e.ld));
-    else if (e.kind == 11) TRY(pack_conv3x3_dgrad_launch(w, d16, e.O, e.I, st));
-    else if (e.kind == 12) TRY(pack_conv3x3_s2_dgrad_launch(w, d16, e.O, e.I, st));
-    else TRY(flip_oihw_launch(w, reinterpret_cast<float*>(e.dst), e.O, e.I, 3, st));
-  }
-  s.loaded = true;
-  return HEDIT_OK;
-} catch (...) { return hedit_abi_catch(); }
-
-int hedit_unet_missing(const hedit_unet* h) try {
-  if (!h) return -1;
-  int m = 0;
-  for (auto& s : h->slots) m += s.loaded ? 0 : 1;
-  return m;
-} catch (...) { return hedit_abi_catch(); }
 
 /* enough for hedit_unet_forward and for hedit_unet_forward_shared under ANY row map: the arena's layout depends on how many
    rows the shared part runs at, so every count of distinct latents gets its dry run (D == B: the latents are spread to one
@@ -1248,10 +1066,7 @@ static int forward_checks(hedit_unet* h, const float* x, const float* ctx, int B
   ARG_CHECK(height % div == 0 && width % div == 0, "latent size must be divisible by 2^(levels-1)");
   const int lowest = (height / div) * (width / div);
   ARG_CHECK(lowest % 64 == 0, "lowest-resolution level must have a multiple of 64 tokens");
-  if (hedit_unet_missing(h) != 0) {
-    hedit_set_error("UNet has " + std::to_string(hedit_unet_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(store_require_loaded(h, "UNet"));
   ARG_CHECK(!(h->hook && plan && plan->mode > 0), "an attention hook excludes the in-kernel edits of a plan (pass plan = NULL)");
   if (plan && plan->mode > 0) {
     ARG_CHECK(plan->n_pairs >= 0 && plan->n_pairs + plan->n_single > 0, "plan rows");
@@ -1299,7 +1114,7 @@ size_t hedit_unet_grad_workspace_bytes(hedit_unet* h, int B, int height, int wid
     if (rc == HEDIT_OK) rc = backward_impl(h, T, &dummy, &dummy, &dummy);
     if (rc == HEDIT_OK) rc = backward_impl(h, T, &dummy, nullptr, &dummy);
   }
-  return rc == HEDIT_OK ? T.f.ar.peak + 4096 : 0;
+  return dry_run_bytes(rc, T.f.ar.peak);
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
 int hedit_unet_forward_keep(hedit_unet* h, const float* x, float t, const float* ctx, int B, int height, int width, float* eps,

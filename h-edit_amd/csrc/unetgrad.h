@@ -569,12 +569,7 @@ int check_grad_handle(hedit_unet* h, const char* who) {
     hedit_set_error(std::string(who) + ": this handle has no input-gradient weights (create it with hedit_unet_create_grad)");
     return HEDIT_ERR_STATE;
   }
-  int missing = 0;
-  for (auto& s : h->slots) missing += s.loaded ? 0 : 1;
-  if (missing) {
-    hedit_set_error("UNet has " + std::to_string(missing) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(store_require_loaded(h, "UNet"));
   if (h->hook) {
     hedit_set_error(std::string(who) + ": the gradient is that of the plain network; clear the attention hook first");
     return HEDIT_ERR_STATE;

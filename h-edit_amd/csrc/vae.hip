@@ -33,7 +33,7 @@ struct VStage {
 
 }  // namespace
 
-struct hedit_vae : ParamStore {
+struct HEDIT_HANDLE hedit_vae : ParamStore {
   hedit_vae_cfg cfg;
   // encoder
   float *e_in_w = nullptr, *e_in_b = nullptr, *e_gn_g = nullptr, *e_gn_b = nullptr, *e_out_b = nullptr;
@@ -282,6 +282,13 @@ int encode_impl(hedit_vae* h, const float* image, int B, int IH, int IW, float* 
 }  // namespace
 
 // ==================================================================================== C ABI
+static void drop_tape(hedit_vae* h) {
+  if (h->tape && h->tape_free) h->tape_free(h->tape);
+  h->tape = nullptr;
+}
+
+HEDIT_LIFECYCLE(vae, hedit_vae, "VAE", drop_tape)
+
 extern "C" {
 
 int hedit_vae_create(const hedit_vae_cfg* cfg, hedit_vae** out) try {
@@ -326,11 +333,11 @@ int hedit_vae_create(const hedit_vae_cfg* cfg, hedit_vae** out) try {
   h->quant_b = vec(h, "quant_conv.bias", 2 * LC);
   // ---- decoder
   h->pq_w = f32conv(h, "post_quant_conv.weight", LC, LC, 1);
-  h->pq_t = twin<float>(h, 3, (size_t)LC * LC);
+  h->pq_t = twin<float>(h, Pack::FlipOIHW, (size_t)LC * LC);
   h->pq_b = vec(h, "post_quant_conv.bias", LC);
   ch = bc[L - 1];
   h->d_in_w = f32conv(h, "decoder.conv_in.weight", ch, LC, 3);
-  h->d_in_t = twin<bf16_t>(h, 2, (size_t)ch * LC * 9);
+  h->d_in_t = twin<bf16_t>(h, Pack::Conv3Dgrad, (size_t)ch * LC * 9);
   h->d_in_b = vec(h, "decoder.conv_in.bias", ch);
   h->d_mid = make_mid(h, "decoder.mid_block", ch, true);
   for (int i = 0; i < L; ++i) {
@@ -344,7 +351,7 @@ int hedit_vae_create(const hedit_vae_cfg* cfg, hedit_vae** out) try {
     s.ch = ch;
     if (i < L - 1) {
       s.samp_w = conv3(h, pre + ".upsamplers.0.conv.weight", ch, ch);
-      s.samp_t = twin<bf16_t>(h, 2, (size_t)ch * ch * 9);
+      s.samp_t = twin<bf16_t>(h, Pack::Conv3Dgrad, (size_t)ch * ch * 9);
       s.samp_b = vec(h, pre + ".upsamplers.0.conv.bias", ch);
     }
     h->up.push_back(s);
@@ -352,7 +359,7 @@ int hedit_vae_create(const hedit_vae_cfg* cfg, hedit_vae** out) try {
   h->d_gn_g = vec(h, "decoder.conv_norm_out.weight", ch);
   h->d_gn_b = vec(h, "decoder.conv_norm_out.bias", ch);
   h->d_out_w = conv3(h, "decoder.conv_out.weight", cfg->in_channels, ch);
-  h->d_out_t = twin<float>(h, 3, (size_t)cfg->in_channels * ch * 9);
+  h->d_out_t = twin<float>(h, Pack::FlipOIHW, (size_t)cfg->in_channels * ch * 9);
   h->d_out_b = vec(h, "decoder.conv_out.bias", cfg->in_channels);
   {
     int zc = 8;
@@ -360,37 +367,8 @@ int hedit_vae_create(const hedit_vae_cfg* cfg, hedit_vae** out) try {
     h->zero_bias = dalloc<float>(h, zc);
     if (h->zero_bias && hipMemset(h->zero_bias, 0, zc * sizeof(float)) != hipSuccess) h->alloc_failed = true;
   }
-  if (h->alloc_failed) {
-    hedit_set_error("hipMalloc failed while creating the VAE");
-    hedit_vae_destroy(h);
-    return HEDIT_ERR_HIP;
-  }
-  *out = h;
-  return HEDIT_OK;
+  return handle_created(h, out);
 } catch (...) { return hedit_abi_catch(); }
-
-static void drop_tape(hedit_vae* h) {
-  if (h->tape && h->tape_free) h->tape_free(h->tape);
-  h->tape = nullptr;
-}
-
-void hedit_vae_destroy(hedit_vae* h) try {
-  if (!h) return;
-  drop_tape(h);
-  store_free(h);
-  delete h;
-} catch (...) { (void)hedit_abi_catch(); }
-
-int hedit_vae_num_params(const hedit_vae* h) { return store_num_params(h); }
-const char* hedit_vae_param_name(const hedit_vae* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_vae_param_shape(const hedit_vae* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
-
-int hedit_vae_load(hedit_vae* h, const char* name, const float* w, size_t numel, void* stream) try {
-  ARG_CHECK(h && name && w, "null");
-  return store_load(h, "VAE", name, w, numel, reinterpret_cast<hipStream_t>(stream));
-} catch (...) { return hedit_abi_catch(); }
-
-int hedit_vae_missing(const hedit_vae* h) { return h ? store_missing(h) : -1; }
 
 static int check_latent(const hedit_vae* h, int lh, int lw) {
   ARG_CHECK(lh >= 1 && lw >= 1 && (lh * lw) % 64 == 0, "latent h*w must be a multiple of 64 (attention tokens)");
@@ -406,7 +384,7 @@ size_t hedit_vae_workspace_bytes(hedit_vae* h, int B, int latent_h, int latent_w
   int rc = encode == 1 ? encode_impl(h, nullptr, B, latent_h * f, latent_w * f, nullptr, nullptr, 0, nullptr, true, &peak)
          : encode == 2 ? decode_impl(h, nullptr, B, latent_h, latent_w, nullptr, nullptr, 0, nullptr, true, &peak, &dummy, &dummy)
                        : decode_impl(h, nullptr, B, latent_h, latent_w, nullptr, nullptr, 0, nullptr, true, &peak);
-  return rc == HEDIT_OK ? peak + 4096 : 0;
+  return dry_run_bytes(rc, peak);
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
 int hedit_vae_decode(hedit_vae* h, const float* z, int B, int latent_h, int latent_w, float* image, void* workspace,
@@ -414,10 +392,7 @@ int hedit_vae_decode(hedit_vae* h, const float* z, int B, int latent_h, int late
   ARG_CHECK(h && z && image && workspace, "null");
   ARG_CHECK(B >= 1, "B");
   TRY(check_latent(h, latent_h, latent_w));
-  if (hedit_vae_missing(h) != 0) {
-    hedit_set_error("VAE has " + std::to_string(hedit_vae_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(handle_loaded(h));
   return decode_impl(h, z, B, latent_h, latent_w, image, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream),
                      false, nullptr);
 } catch (...) { return hedit_abi_catch(); }
@@ -427,10 +402,7 @@ int hedit_vae_decode_vjp(hedit_vae* h, const float* z, const float* d_image, int
   ARG_CHECK(h && z && d_image && d_z && workspace, "null");
   ARG_CHECK(B >= 1, "B");
   TRY(check_latent(h, latent_h, latent_w));
-  if (hedit_vae_missing(h) != 0) {
-    hedit_set_error("VAE has " + std::to_string(hedit_vae_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(handle_loaded(h));
   return decode_impl(h, z, B, latent_h, latent_w, image, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream),
                      false, nullptr, d_image, d_z);
 } catch (...) { return hedit_abi_catch(); }
@@ -440,10 +412,7 @@ int hedit_vae_decode_keep(hedit_vae* h, const float* z, int B, int latent_h, int
   ARG_CHECK(h && z && image && workspace, "null");
   ARG_CHECK(B >= 1, "B");
   TRY(check_latent(h, latent_h, latent_w));
-  if (hedit_vae_missing(h) != 0) {
-    hedit_set_error("VAE has " + std::to_string(hedit_vae_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(handle_loaded(h));
   drop_tape(h);
   DecodeTape* T = new DecodeTape();
   tape_init(*T, h, B, latent_h, latent_w, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false);
@@ -481,10 +450,7 @@ int hedit_vae_encode(hedit_vae* h, const float* image, int B, int height, int wi
   const int f = 1 << (h->cfg.n_levels - 1);
   ARG_CHECK(height % f == 0 && width % f == 0, "image size must be divisible by 2^(levels-1)");
   TRY(check_latent(h, height / f, width / f));
-  if (hedit_vae_missing(h) != 0) {
-    hedit_set_error("VAE has " + std::to_string(hedit_vae_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(handle_loaded(h));
   return encode_impl(h, image, B, height, width, mean, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream),
                      false, nullptr);
 } catch (...) { return hedit_abi_catch(); }

@@ -321,13 +321,12 @@ inline int attn_slices(int heads, int B) {
 
 }  // namespace
 
-struct hedit_vit : ParamStore {
+struct HEDIT_HANDLE hedit_vit : ParamStore {
   hedit_vit_cfg cfg;
   int L = 0, P = 0;
   float *conv_w = nullptr, *cls = nullptr, *pos = nullptr, *lnpg = nullptr, *lnpb = nullptr;
   PConv conv;
   std::vector<EncBlock> blocks;
-  bool finalized = false;
 };
 
 namespace {
@@ -335,8 +334,8 @@ namespace {
 struct BTape { float *Tin, *st1, *qkv, *A, *lse, *Tmid, *st2, *H; };
 
 int ln_fwd(PF& f, const float* x, const float* g, const float* b, long rows, int W, float** y, float** stats) {
-  TRY(palloc(f, y, (size_t)rows * W));
-  TRY(palloc(f, stats, (size_t)rows * 2));
+  TRY(aalloc(f, y, (size_t)rows * W));
+  TRY(aalloc(f, stats, (size_t)rows * 2));
   return ln(f, x, g, b, rows, W, LN_EPS, *y, *stats);
 }
 
@@ -350,11 +349,11 @@ int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int
   const float ascale = 1.0f / sqrtf((float)(W / heads));
   const bool grad = want_grad;
   float *X0, *E, *T0, *T, *stp;
-  TRY(palloc(f, &X0, (size_t)Mp * K0));
+  TRY(aalloc(f, &X0, (size_t)Mp * K0));
   if (!dry) TRY(enc_patchify_launch(img, X0, B, R, p, 0, st));
   TRY(lin(f, X0, K0, P_COPY, nullptr, nullptr, h->conv, false, Mp, &E));
   f.ar.free(X0);
-  TRY(palloc(f, &T0, (size_t)M * W));
+  TRY(aalloc(f, &T0, (size_t)M * W));
   if (!dry) TRY(enc_tokens_launch(E, nullptr, h->cls, h->pos, T0, B, L, W, st));
   f.ar.free(E);
   TRY(ln_fwd(f, T0, h->lnpg, h->lnpb, M, W, &T, &stp));
@@ -368,14 +367,14 @@ int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int
     TRY(ln_fwd(f, T, k.ln1g, k.ln1b, M, W, &a, &t.st1));
     TRY(lin(f, a, W, P_COPY, nullptr, nullptr, k.in, false, M, &t.qkv));
     f.ar.free(a);
-    TRY(palloc(f, &t.A, (size_t)M * W));
-    TRY(palloc(f, &t.lse, (size_t)B * heads * L));
+    TRY(aalloc(f, &t.A, (size_t)M * W));
+    TRY(aalloc(f, &t.lse, (size_t)B * heads * L));
     if (!dry) {
       hipLaunchKernelGGL(attn_fwd_kernel, dim3(heads, B, attn_slices(heads, B)), dim3(256), ATTN_LDS_FWD, st, t.qkv, k.bin, t.A, t.lse, L, W, ascale);
       LAUNCH_CHECK();
     }
     TRY(lin(f, t.A, W, P_COPY, nullptr, nullptr, k.out, false, M, &raw));
-    TRY(palloc(f, &t.Tmid, (size_t)M * W));
+    TRY(aalloc(f, &t.Tmid, (size_t)M * W));
     if (!dry) TRY(enc_add_bias_res_launch(raw, k.bo, t.Tin, t.Tmid, M * W, W, st));
     f.ar.free(raw);
     TRY(ln_fwd(f, t.Tmid, k.ln2g, k.ln2b, M, W, &m, &t.st2));
@@ -383,7 +382,7 @@ int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int
     f.ar.free(m);
     TRY(lin(f, t.H, 4 * W, P_QGELU, k.bfc, nullptr, k.proj, false, M, &raw));
     float* Tn;
-    TRY(palloc(f, &Tn, (size_t)M * W));
+    TRY(aalloc(f, &Tn, (size_t)M * W));
     if (!dry) TRY(enc_add_bias_res_launch(raw, k.bp, t.Tmid, Tn, M * W, W, st));
     f.ar.free(raw);
     if (!grad) {
@@ -394,8 +393,8 @@ int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int
   // ---- Gram matrix of the patch tokens, per image
   const int Lp = (L - 1 + 63) / 64 * 64;
   float *Ft, *G, *nrm = nullptr, *dT = nullptr, *gpart = nullptr;
-  TRY(palloc(f, &Ft, (size_t)W * Lp));
-  if (grad) { TRY(palloc(f, &nrm, (size_t)B)); TRY(palloc(f, &gpart, (size_t)GR_BLOCKS)); TRY(palloc(f, &dT, (size_t)M * W)); }
+  TRY(aalloc(f, &Ft, (size_t)W * Lp));
+  if (grad) { TRY(aalloc(f, &nrm, (size_t)B)); TRY(aalloc(f, &gpart, (size_t)GR_BLOCKS)); TRY(aalloc(f, &dT, (size_t)M * W)); }
   PConv gc;                       // "weights" = the second activation operand of F^T F / F R
   for (int b = 0; b < B; ++b) {
     const float* Tb = T + (size_t)b * L * W;
@@ -405,7 +404,7 @@ int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int
     {
       Split3Params s{};
       s.x = Ft; s.ldx = Lp; s.op = P_COPY; s.Kp = split_kp(Lp); s.Cs = split_cs(Lp); s.C = Lp; s.B = 1; s.H = 1; s.W = 1; s.worder = 1;
-      TRY(palloc(f, &A2, (size_t)W * s.Kp));
+      TRY(aalloc(f, &A2, (size_t)W * s.Kp));
       s.out = A2;
       if (!dry) TRY(split3_launch(s, W, st));
     }
@@ -434,7 +433,7 @@ int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int
     {
       Split3Params s{};
       s.x = G; s.ldx = W; s.op = P_COPY; s.Kp = split_kp(W); s.Cs = split_cs(W); s.C = W; s.B = 1; s.H = 1; s.W = 1; s.worder = 1;
-      TRY(palloc(f, &AR, (size_t)W * s.Kp));
+      TRY(aalloc(f, &AR, (size_t)W * s.Kp));
       s.out = AR;
       if (!dry) TRY(split3_launch(s, W, st));
     }
@@ -469,11 +468,11 @@ int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int
     TRY(lin(f, dG, 4 * W, P_QGELU_GRAD, k.bfc, t.H, k.fc, true, M, &dm));                        // d LN2 output
     f.ar.free(dG);
     f.ar.free(t.H);
-    TRY(palloc(f, &dTm, (size_t)M * W));
+    TRY(aalloc(f, &dTm, (size_t)M * W));
     if (!dry) { hipLaunchKernelGGL(ln_bwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, t.Tmid, dm, k.ln2g, t.st2, dT, dTm, M, W); LAUNCH_CHECK(); }
     f.ar.free(dm); f.ar.free(dT); f.ar.free(t.Tmid); f.ar.free(t.st2);
     TRY(lin(f, dTm, W, P_COPY, nullptr, nullptr, k.out, true, M, &dAo));                         // d attention output
-    TRY(palloc(f, &dqkv, (size_t)M * 3 * W));
+    TRY(aalloc(f, &dqkv, (size_t)M * 3 * W));
     if (!dry) {
       hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(heads, B, attn_slices(heads, B)), dim3(256), ATTN_LDS_DQ, st, t.qkv, k.bin, t.A, dAo, t.lse, dqkv, L, W, ascale);
       LAUNCH_CHECK();
@@ -483,17 +482,17 @@ int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int
     f.ar.free(dAo); f.ar.free(t.qkv); f.ar.free(t.A); f.ar.free(t.lse);
     TRY(lin(f, dqkv, 3 * W, P_COPY, nullptr, nullptr, k.in, true, M, &da));                      // d LN1 output
     f.ar.free(dqkv);
-    TRY(palloc(f, &dTi, (size_t)M * W));
+    TRY(aalloc(f, &dTi, (size_t)M * W));
     if (!dry) { hipLaunchKernelGGL(ln_bwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, t.Tin, da, k.ln1g, t.st1, dTm, dTi, M, W); LAUNCH_CHECK(); }
     f.ar.free(da); f.ar.free(dTm); f.ar.free(t.Tin); f.ar.free(t.st1);
     dT = dTi;
   }
   // ln_pre, class token, patch embedding
   float *dT0, *dE, *dX0;
-  TRY(palloc(f, &dT0, (size_t)M * W));
+  TRY(aalloc(f, &dT0, (size_t)M * W));
   if (!dry) { hipLaunchKernelGGL(ln_bwd_kernel, dim3(cdiv(M, 4)), dim3(256), 0, st, T0, dT, h->lnpg, stp, (const float*)nullptr, dT0, M, W); LAUNCH_CHECK(); }
   f.ar.free(dT); f.ar.free(T0); f.ar.free(stp);
-  TRY(palloc(f, &dE, (size_t)Mp * W));
+  TRY(aalloc(f, &dE, (size_t)Mp * W));
   if (!dry) { hipLaunchKernelGGL(drop_cls_kernel, egrid(Mp * W), dim3(256), 0, st, dT0, dE, B, L, W); LAUNCH_CHECK(); }
   f.ar.free(dT0);
   TRY(lin(f, dE, W, P_COPY, nullptr, nullptr, h->conv, true, Mp, &dX0));
@@ -505,6 +504,8 @@ int run(hedit_vit* h, const float* img, const float* gref, long gref_stride, int
 }
 
 }  // namespace
+
+HEDIT_LIFECYCLE(vit, hedit_vit, "ViT", no_pre_destroy)
 
 extern "C" {
 
@@ -527,38 +528,12 @@ int hedit_vit_create(const hedit_vit_cfg* cfg, hedit_vit** out) try {
   h->lnpb = vec(h, "visual.ln_pre.bias", W);
   for (int i = 0; i < cfg->layers; ++i)
     h->blocks.push_back(enc_add_block(h, "visual.transformer.resblocks." + std::to_string(i), CLIP_BLOCK_NAMES, W));
-  if (h->alloc_failed) {
-    hedit_set_error("hipMalloc failed while creating the ViT prefix");
-    store_free(h);
-    delete h;
-    return HEDIT_ERR_HIP;
-  }
-  *out = h;
-  return HEDIT_OK;
+  return handle_created(h, out);
 } catch (...) { return hedit_abi_catch(); }
-
-void hedit_vit_destroy(hedit_vit* h) try {
-  if (!h) return;
-  store_free(h);
-  delete h;
-} catch (...) { (void)hedit_abi_catch(); }
-
-int hedit_vit_num_params(const hedit_vit* h) { return store_num_params(h); }
-const char* hedit_vit_param_name(const hedit_vit* h, int i) try { return store_param_name(h, i); } catch (...) { (void)hedit_abi_catch(); return nullptr; }
-int hedit_vit_param_shape(const hedit_vit* h, int i, int* ndim, int* dims4) try { return store_param_shape(h, i, ndim, dims4); } catch (...) { return hedit_abi_catch(); }
-int hedit_vit_load(hedit_vit* h, const char* name, const float* w, size_t numel, void* stream) try {
-  ARG_CHECK(h && name && w, "null");
-  h->finalized = false;
-  return store_load(h, "ViT", name, w, numel, reinterpret_cast<hipStream_t>(stream));
-} catch (...) { return hedit_abi_catch(); }
-int hedit_vit_missing(const hedit_vit* h) { return h ? store_missing(h) : -1; }
 
 int hedit_vit_finalize(hedit_vit* h, void* stream) try {
   ARG_CHECK(h, "null");
-  if (store_missing(h) != 0) {
-    hedit_set_error("ViT has " + std::to_string(store_missing(h)) + " unloaded parameters");
-    return HEDIT_ERR_STATE;
-  }
+  TRY(handle_loaded(h));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const int W = h->cfg.width, p = h->cfg.patch_size;
   // conv1 weight [W][3][p][p] flattened = a linear map over (c, ky, kx): k = 1 with I = 3 p^2
@@ -576,15 +551,15 @@ int hedit_vit_finalize(hedit_vit* h, void* stream) try {
 size_t hedit_vit_workspace_bytes(hedit_vit* h, int B) try {
   if (!h || B < 1) return 0;
   size_t peak = 0;
-  if (run(h, nullptr, nullptr, 0, B, 1.f, nullptr, nullptr, nullptr, nullptr, 0, nullptr, true, true, &peak) != HEDIT_OK) return 0;
-  return peak + 4096;
+  const int rc = run(h, nullptr, nullptr, 0, B, 1.f, nullptr, nullptr, nullptr, nullptr, 0, nullptr, true, true, &peak);
+  return dry_run_bytes(rc, peak);
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
 /* image fp32 [B][3][R][R], CLIP-normalised and resized -> gram fp32 [B][W][W]: F^T F of the patch tokens after the last
  * kept block (the style reference's side of get_gram_matrix_residual, base_clip.py:60-65) */
 int hedit_vit_gram(hedit_vit* h, const float* image, int B, float* gram, void* workspace, size_t workspace_bytes, void* stream) try {
   ARG_CHECK(h && image && gram && workspace && B >= 1, "vit_gram args");
-  if (!h->finalized) { hedit_set_error("call hedit_vit_finalize after loading the parameters"); return HEDIT_ERR_STATE; }
+  TRY(handle_finalized(h));
   return run(h, image, nullptr, 0, B, 1.f, gram, nullptr, nullptr, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream), false,
              false, nullptr);
 } catch (...) { return hedit_abi_catch(); }
@@ -595,7 +570,7 @@ int hedit_vit_gram(hedit_vit* h, const float* image, int B, float* gram, void* w
 int hedit_vit_gram_fwd_bwd(hedit_vit* h, const float* image, const float* gram_ref, int ref_per_image, int B, float scale, float* loss,
                            float* d_image, void* workspace, size_t workspace_bytes, void* stream) try {
   ARG_CHECK(h && image && gram_ref && loss && d_image && workspace && B >= 1, "vit_gram_fwd_bwd args");
-  if (!h->finalized) { hedit_set_error("call hedit_vit_finalize after loading the parameters"); return HEDIT_ERR_STATE; }
+  TRY(handle_finalized(h));
   const long stride = ref_per_image ? (long)h->cfg.width * h->cfg.width : 0;
   return run(h, image, gram_ref, stride, B, scale, nullptr, loss, d_image, workspace, workspace_bytes, reinterpret_cast<hipStream_t>(stream),
              false, true, nullptr);
