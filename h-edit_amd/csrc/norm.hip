@@ -635,9 +635,11 @@ __global__ __launch_bounds__(256) void conv_out_kernel(const bf16_t* __restrict_
 // strided pairs, butterfly over the wave, waves 0..3 in order: a function of the image alone, like every norm here) and
 // normalises from LDS.  Three launches (partials, finalize, apply) became one; at one image per call that is 60 launches
 // of a UNet pass.
-__global__ __launch_bounds__(256) void gn_small_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
-                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                       int HW, int C, int G, float eps, int silu, float* __restrict__ stats) {
+// This is the first form of it, 4 bytes per lane straight from the strided slice, grid (G, B): kept as the reference bits of
+// gn_small_kernel below (hedit_test_set_flags bit 4 launches it; tests/test_gpu_gn_small_bits.py, tools/gn_small_bench.py).
+__global__ __launch_bounds__(256) void gn_small_narrow_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
+                                                              const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                              int HW, int C, int G, float eps, int silu, float* __restrict__ stats) {
   extern __shared__ uint32_t gs_pairs[];
   __shared__ float red[8];
   const int g = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
@@ -675,6 +677,107 @@ __global__ __launch_bounds__(256) void gn_small_kernel(const bf16_t* __restrict_
     float c = st_hi(u) * sc1 + (beta[c0 + 1] - m * sc1);
     if (silu) { a = silu_f(a); c = silu_f(c); }
     yout[(long)pix * (C / 2) + j] = pack_bf16x2(a, c);
+  }
+}
+
+// The same bits at memory speed.  What the narrow form pays for: a wave's 4-byte loads cover 3.2 pixels' 80-byte slices (C = 1280)
+// in 64 lanes -- 20 load and 20 store instructions per thread at 16 x 16, each touching four or five 128-byte lines in part --, and
+// with the group index fastest in the grid the 32 groups of an image spread over all eight XCDs, so every line that straddles two
+// groups is fetched into two L2s and written from two.  Here
+//   * the slice enters LDS in NW-word vectors (16 / 8 / 4 bytes, the widest the slice's width and base allow), one pixel's slice
+//     per run of consecutive lanes, GS_U vectors in flight per thread, into the SAME canonical pair layout (pair i = pix * ppp + j
+//     at word i: vector v of the block is words v * NW ..);
+//   * after a barrier the sums read LDS in the narrow kernel's order -- thread tid takes pairs tid, tid + 256, .. with the same
+//     four additions, butterfly over the wave, waves 0..3 in order -- so (mean, rstd) are its bits;
+//   * the per-channel scale and shift (rstd * gamma, beta - mean * scale: the narrow kernel's expressions) are computed once per
+//     block into LDS, and the store phase normalises from LDS with the narrow kernel's two operations per element, NW words a store;
+//   * the grid is one-dimensional and padded to a multiple of 8: block bid works for image (bid & 7) + 8 * (slot / G), group
+//     slot % G with slot = bid >> 3.  Blocks are dealt round-robin over the XCDs, so the groups of one image run on one XCD and next
+//     to each other in time (a matter of speed only: nothing here depends on where a block runs).
+// The path is chosen by (HW, C, G) and the pointers' alignment, never by the batch.
+template <int NW>
+using gs_vec = uint32_t __attribute__((ext_vector_type(NW)));
+constexpr int GS_U = 5;   // vectors requested per thread before the first is parked (16 x 16, C = 1280: all five of a thread)
+
+template <int NW>
+__global__ __launch_bounds__(256) void gn_small_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
+                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                       int HW, int C, int G, int B, float eps, int silu, float* __restrict__ stats) {
+  typedef gs_vec<NW> V;
+  extern __shared__ uint4 gs_wide[];                    // [HW * ppp] pairs, then scale[cpg], shift[cpg]
+  __shared__ float red[8];
+  const int tid = threadIdx.x;
+  const int slot = blockIdx.x >> 3, slot_img = slot / G;
+  const int b = (blockIdx.x & 7) + 8 * slot_img, g = slot - slot_img * G;
+  if (b >= B) return;                                   // (the padding of the last eight images: whole blocks, before any barrier)
+  const int cpg = C / G, ppp = cpg / 2, vpp = ppp / NW; // bf16 pairs / vectors per pixel of this group
+  const int npair = HW * ppp, nvec = HW * vpp;
+  const int rowv = C / (2 * NW);                        // vectors per pixel of the tensor
+  uint32_t* pairs = reinterpret_cast<uint32_t*>(gs_wide);
+  V* vecs = reinterpret_cast<V*>(gs_wide);
+  float* scale = reinterpret_cast<float*>(pairs + npair);
+  float* shift = scale + cpg;
+  // vector v = tid, tid + 256, .. is (pixel v / vpp, vector v % vpp of its slice): one division, then steps of 256
+  const int dq = 256 / vpp, dr = 256 - dq * vpp;
+  {
+    const V* xin = reinterpret_cast<const V*>(x + (long)b * HW * C + g * cpg);
+    int pix = tid / vpp, k = tid - pix * vpp;
+    for (int v0 = tid; v0 < nvec; v0 += 256 * GS_U) {
+      V r[GS_U];
+#pragma unroll
+      for (int u = 0; u < GS_U; ++u) {
+        r[u] = V(0);
+        if (v0 + u * 256 < nvec) r[u] = xin[(long)pix * rowv + k];
+        pix += dq; k += dr;
+        if (k >= vpp) { k -= vpp; ++pix; }
+      }
+#pragma unroll
+      for (int u = 0; u < GS_U; ++u)
+        if (v0 + u * 256 < nvec) vecs[v0 + u * 256] = r[u];
+    }
+  }
+  __syncthreads();
+  float s = 0.f, q = 0.f;
+  for (int i = tid; i < npair; i += 256) {
+    const uint32_t u = pairs[i];
+    const float a = st_lo(u), c = st_hi(u);
+    s += a; s += c;
+    q += a * a; q += c * c;
+  }
+  s = wave_sum(s);
+  q = wave_sum(q);
+  if ((tid & 63) == 0) { red[(tid >> 6) * 2] = s; red[(tid >> 6) * 2 + 1] = q; }
+  __syncthreads();
+  s = ((red[0] + red[2]) + red[4]) + red[6];
+  q = ((red[1] + red[3]) + red[5]) + red[7];
+  const float n = (float)HW * (float)cpg;
+  const float m = s / n;
+  float var = q / n - m * m;
+  var = var < 0.f ? 0.f : var;
+  const float rstd = rsqrtf(var + eps);
+  if (stats && tid == 0) *reinterpret_cast<float2*>(stats + ((long)b * G + g) * 2) = make_float2(m, rstd);
+  for (int c = tid; c < cpg; c += 256) {
+    const float sc = rstd * gamma[g * cpg + c];
+    scale[c] = sc;
+    shift[c] = beta[g * cpg + c] - m * sc;
+  }
+  __syncthreads();
+  V* yout = reinterpret_cast<V*>(y + (long)b * HW * C + g * cpg);
+  int pix = tid / vpp, k = tid - pix * vpp;
+  for (int v = tid; v < nvec; v += 256) {
+    const V u = vecs[v];
+    V o;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      const int c0 = 2 * (k * NW + w);
+      float a = st_lo(u[w]) * scale[c0] + shift[c0];
+      float c = st_hi(u[w]) * scale[c0 + 1] + shift[c0 + 1];
+      if (silu) { a = silu_f(a); c = silu_f(c); }
+      o[w] = pack_bf16x2(a, c);
+    }
+    yout[(long)pix * rowv + k] = o;
+    pix += dq; k += dr;
+    if (k >= vpp) { k -= vpp; ++pix; }
   }
 }
 
@@ -738,7 +841,20 @@ int groupnorm_launch(const bf16_t* x, bf16_t* y, const float* gamma, const float
   ARG_CHECK(C / 8 <= 256 * GN_MAXV, "groupnorm: C too large");
   // small images: one launch (a choice by (HW, C, G) only, never by the batch)
   if (HW < 1024 && (C / G) % 2 == 0 && (size_t)HW * (C / G) * 2 <= 60 * 1024) {
-    hipLaunchKernelGGL(gn_small_kernel, dim3(G, B), dim3(256), (size_t)HW * (C / G) * 2, st, x, y, gamma, beta, HW, C, G, eps, silu, stats);
+    const int cpg = C / G;
+    const size_t lds = (size_t)HW * cpg * 2 + (size_t)cpg * 2 * sizeof(float);   // the pairs, then scale and shift per channel
+    if ((hedit_test_flags() & 16) || lds > 64 * 1024) {     // tests / tools: the kept narrow form (same bits); or no room for the tables
+      hipLaunchKernelGGL(gn_small_narrow_kernel, dim3(G, B), dim3(256), (size_t)HW * cpg * 2, st, x, y, gamma, beta, HW, C, G, eps, silu, stats);
+      LAUNCH_CHECK();
+      return HEDIT_OK;
+    }
+    // widest vector that divides the slice (C % 8 == 0 keeps every pixel's slice as aligned as the first) and both bases
+    const uintptr_t al = (uintptr_t)x | (uintptr_t)y;
+    const int nw = (cpg * 2) % 16 == 0 && al % 16 == 0 ? 4 : ((cpg * 2) % 8 == 0 && al % 8 == 0 ? 2 : 1);
+    const dim3 grid((unsigned)((B + 7) / 8 * 8 * G));
+    if (nw == 4) hipLaunchKernelGGL(gn_small_kernel<4>, grid, dim3(256), lds, st, x, y, gamma, beta, HW, C, G, B, eps, silu, stats);
+    else if (nw == 2) hipLaunchKernelGGL(gn_small_kernel<2>, grid, dim3(256), lds, st, x, y, gamma, beta, HW, C, G, B, eps, silu, stats);
+    else hipLaunchKernelGGL(gn_small_kernel<1>, grid, dim3(256), lds, st, x, y, gamma, beta, HW, C, G, B, eps, silu, stats);
     LAUNCH_CHECK();
     return HEDIT_OK;
   }

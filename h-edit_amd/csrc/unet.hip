@@ -668,11 +668,46 @@ int broadcast_stem(Fwd& f, size_t row_elems, bf16_t** x, bf16_t** t1, bf16_t** q
   return HEDIT_OK;
 }
 
+// The text context of a call: fp32 [B][77][ctx_dim] -> bf16 padded to 80 rows per item, then the attn2 keys / values of ALL
+// transformer blocks in two launches.  They stay live for the whole pass (the blocks read their column / row slice):
+// 2 * B * 80 * ctx_n * 2 bytes = 4 MB per batch row for SD-1.5 (ctx_n = 12480), 0.48 GB at the bench's 120 rows -- arena
+// allocations like every other (hedit_unet_workspace_bytes counts them), or the memory of a hedit_unet_context, which runs this
+// very routine once (hedit_unet_context_create) for the calls that are handed the object instead of the fp32 rows.
+int project_context(Fwd& f, const float* ctx) {
+  hedit_unet* h = f.h;
+  const hedit_unet_cfg& c = h->cfg;
+  const int MC = f.B * HEDIT_CTXP;
+  bf16_t *ctxb, *k2a, *vt2a;
+  TRY(aalloc(f, &ctxb, (size_t)MC * c.cross_attention_dim));
+  RUN(f, ctx_pad_launch(ctx, ctxb, f.B, c.cross_attention_dim, f.st));
+  f.ctxb = ctxb;
+  TRY(aalloc(f, &k2a, (size_t)MC * h->ctx_n));
+  TRY(aalloc(f, &vt2a, (size_t)MC * h->ctx_n));
+  TRY(linear(f, ctxb, MC, c.cross_attention_dim, h->wk2_all, h->ctx_n, nullptr, nullptr, k2a, h->ctx_n));
+  TRY(linear(f, h->wv2_all, h->ctx_n, c.cross_attention_dim, ctxb, MC, nullptr, nullptr, vt2a, MC, 2));
+  f.k2_all = k2a;
+  f.vt2_all = vt2a;
+  return HEDIT_OK;
+}
+
+}  // namespace
+
+// include/hedit.h: a snapshot of project_context's three results for `B` rows, in memory of its own
+struct HEDIT_HANDLE hedit_unet_context {
+  const hedit_unet* owner = nullptr;     // compared, never dereferenced: the object may outlive its network
+  int B = 0;
+  void* buf = nullptr;
+  const bf16_t *ctxb = nullptr, *k2_all = nullptr, *vt2_all = nullptr;
+};
+
+namespace {
+
 // D == 0: x holds one latent per batch row.  D > 0 (hedit_unet_forward_shared): x holds D distinct latents and row r
-// evaluates latent map->src[r]; a dry run takes the row COUNT only (map == nullptr).
+// evaluates latent map->src[r]; a dry run takes the row COUNT only (map == nullptr).  cx: the projected context of these B rows
+// (then ctx is not read and the three launches of project_context are skipped).
 int forward_impl(hedit_unet* h, const float* x, float t, const float* ctx, int B, int H0, int W0,
                  const hedit_p2p_plan* plan, float* eps_out, void* ws, size_t ws_bytes, hipStream_t st,
-                 bool dry, size_t* peak, int D = 0, const RowMap* map = nullptr) {
+                 bool dry, size_t* peak, int D = 0, const RowMap* map = nullptr, const hedit_unet_context* cx = nullptr) {
   const hedit_unet_cfg& c = h->cfg;
   Fwd f;
   f.h = h; f.B = B; f.st = st; f.plan = plan; f.map = map;
@@ -684,23 +719,11 @@ int forward_impl(hedit_unet* h, const float* x, float t, const float* ctx, int B
     return HEDIT_ERR_ARG;
   }
 
-  // ---- text context -> bf16, padded to 80 rows per item
-  bf16_t* ctxb;
-  TRY(aalloc(f, &ctxb, (size_t)B * HEDIT_CTXP * c.cross_attention_dim));
-  RUN(f, ctx_pad_launch(ctx, ctxb, B, c.cross_attention_dim, st));
-  f.ctxb = ctxb;
-  {
-    // attn2 keys / values of ALL transformer blocks, two launches; they stay live for the whole pass (the blocks read
-    // their column / row slice): 2 * B * 80 * ctx_n * 2 bytes of workspace = 4 MB per batch row for SD-1.5 (ctx_n = 12480),
-    // 0.48 GB at the bench's 120 rows, accounted for by hedit_unet_workspace_bytes like every other arena allocation
-    const int MC = B * HEDIT_CTXP;
-    bf16_t *k2a, *vt2a;
-    TRY(aalloc(f, &k2a, (size_t)MC * h->ctx_n));
-    TRY(aalloc(f, &vt2a, (size_t)MC * h->ctx_n));
-    TRY(linear(f, ctxb, MC, c.cross_attention_dim, h->wk2_all, h->ctx_n, nullptr, nullptr, k2a, h->ctx_n));
-    TRY(linear(f, h->wv2_all, h->ctx_n, c.cross_attention_dim, ctxb, MC, nullptr, nullptr, vt2a, MC, 2));
-    f.k2_all = k2a;
-    f.vt2_all = vt2a;
+  // ---- text context
+  if (cx) {
+    f.ctxb = cx->ctxb; f.k2_all = cx->k2_all; f.vt2_all = cx->vt2_all;
+  } else {
+    TRY(project_context(f, ctx));
   }
 
   // ---- time embedding chain (the timestep is shared by the batch, so this is one GEMV chain)
@@ -1058,7 +1081,7 @@ size_t hedit_unet_workspace_bytes(hedit_unet* h, int B, int height, int width) t
   return need;
 } catch (...) { (void)hedit_abi_catch(); return 0; }
 
-static int forward_checks(hedit_unet* h, const float* x, const float* ctx, int B, int height, int width, const hedit_p2p_plan* plan,
+static int forward_checks(hedit_unet* h, const float* x, const void* ctx, int B, int height, int width, const hedit_p2p_plan* plan,
                           float* eps_out, void* workspace) {
   ARG_CHECK(h && x && ctx && eps_out && workspace, "null");
   ARG_CHECK(B >= 1, "B");
@@ -1083,23 +1106,100 @@ int hedit_unet_forward(hedit_unet* h, const float* x, float t, const float* ctx,
                       reinterpret_cast<hipStream_t>(stream), false, nullptr);
 } catch (...) { return hedit_abi_catch(); }
 
-int hedit_unet_forward_shared(hedit_unet* h, const float* x, int D, const int* row_latent, float t, const float* ctx, int B,
-                              int height, int width, const hedit_p2p_plan* plan, float* eps_out, void* workspace,
-                              size_t workspace_bytes, void* stream) try {
-  TRY(forward_checks(h, x, ctx, B, height, width, plan, eps_out, workspace));
+static int row_map_checks(const float* x, int D, const int* row_latent, int B, RowMap* map) {
   ARG_CHECK(row_latent && D >= 1 && D <= 65535, "row map");
   if (B > HEDIT_ROWMAP_MAX) {
     hedit_set_error("batch larger than " + std::to_string(HEDIT_ROWMAP_MAX) + " rows (the row map of shared latents)");
     return HEDIT_ERR_ARG;
   }
   ARG_CHECK(reinterpret_cast<uintptr_t>(x) % 16 == 0, "x must be 16-byte aligned");
-  RowMap map{};      // handed to the kernels by value: nothing to upload, nothing to keep alive
   for (int r = 0; r < B; ++r) {
     ARG_CHECK(row_latent[r] >= 0 && row_latent[r] < D, "row_latent entries must lie in [0, D)");
-    map.src[r] = (uint16_t)row_latent[r];
+    map->src[r] = (uint16_t)row_latent[r];
   }
+  return HEDIT_OK;
+}
+
+int hedit_unet_forward_shared(hedit_unet* h, const float* x, int D, const int* row_latent, float t, const float* ctx, int B,
+                              int height, int width, const hedit_p2p_plan* plan, float* eps_out, void* workspace,
+                              size_t workspace_bytes, void* stream) try {
+  TRY(forward_checks(h, x, ctx, B, height, width, plan, eps_out, workspace));
+  RowMap map{};      // handed to the kernels by value: nothing to upload, nothing to keep alive
+  TRY(row_map_checks(x, D, row_latent, B, &map));
   return forward_impl(h, x, t, ctx, B, height, width, plan, eps_out, workspace, workspace_bytes,
                       reinterpret_cast<hipStream_t>(stream), false, nullptr, D, &map);
+} catch (...) { return hedit_abi_catch(); }
+
+// ---- a bound text context
+int hedit_unet_context_create(hedit_unet* h, const float* ctx, int B, void* stream, hedit_unet_context** out) try {
+  ARG_CHECK(h && ctx && out, "null");
+  ARG_CHECK(B >= 1, "B");
+  TRY(store_require_loaded(h, "UNet"));
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIP_TRY(hipStreamIsCapturing(st, &cap));
+  if (cap != hipStreamCaptureStatusNone) {
+    hedit_set_error("hedit_unet_context_create allocates: not while the stream is capturing");
+    return HEDIT_ERR_STATE;
+  }
+  Fwd f;
+  f.h = h; f.B = B; f.st = st; f.plan = nullptr;
+  f.ar.dry = true;
+  TRY(project_context(f, nullptr));
+  const size_t bytes = f.ar.peak;
+  void* buf = nullptr;
+  if (hipMalloc(&buf, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    hedit_set_error("hedit_unet_context_create: out of device memory (" + std::to_string(bytes) + " bytes)");
+    return HEDIT_ERR_HIP;
+  }
+  Fwd g;
+  g.h = h; g.B = B; g.st = st; g.plan = nullptr;
+  g.ar.base = reinterpret_cast<char*>(buf); g.ar.cap = bytes;
+  const int rc = project_context(g, ctx);
+  if (rc != HEDIT_OK) {
+    (void)hipFree(buf);
+    return rc;
+  }
+  hedit_unet_context* cx = new hedit_unet_context();
+  cx->owner = h; cx->B = B; cx->buf = buf;
+  cx->ctxb = g.ctxb; cx->k2_all = g.k2_all; cx->vt2_all = g.vt2_all;
+  *out = cx;
+  return HEDIT_OK;
+} catch (...) { return hedit_abi_catch(); }
+
+void hedit_unet_context_destroy(hedit_unet_context* cx) try {
+  if (!cx) return;
+  (void)hipFree(cx->buf);      // (waits for the device: no launch that reads it is left)
+  delete cx;
+} catch (...) { (void)hedit_abi_catch(); }
+
+static int context_checks(const hedit_unet* h, const hedit_unet_context* cx, int B) {
+  ARG_CHECK(cx, "null context");
+  ARG_CHECK(cx->owner == h, "the context was created on another UNet handle");
+  ARG_CHECK(cx->B == B, "the context was created for another number of rows");
+  ARG_CHECK(!h->hook, "an attention hook takes the fp32 context rows (hedit_unet_forward)");
+  return HEDIT_OK;
+}
+
+int hedit_unet_forward_bound(hedit_unet* h, const float* x, float t, const hedit_unet_context* cx, int B, int height, int width,
+                             const hedit_p2p_plan* plan, float* eps_out, void* workspace, size_t workspace_bytes,
+                             void* stream) try {
+  TRY(forward_checks(h, x, cx, B, height, width, plan, eps_out, workspace));
+  TRY(context_checks(h, cx, B));
+  return forward_impl(h, x, t, nullptr, B, height, width, plan, eps_out, workspace, workspace_bytes,
+                      reinterpret_cast<hipStream_t>(stream), false, nullptr, 0, nullptr, cx);
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_unet_forward_shared_bound(hedit_unet* h, const float* x, int D, const int* row_latent, float t,
+                                    const hedit_unet_context* cx, int B, int height, int width, const hedit_p2p_plan* plan,
+                                    float* eps_out, void* workspace, size_t workspace_bytes, void* stream) try {
+  TRY(forward_checks(h, x, cx, B, height, width, plan, eps_out, workspace));
+  TRY(context_checks(h, cx, B));
+  RowMap map{};
+  TRY(row_map_checks(x, D, row_latent, B, &map));
+  return forward_impl(h, x, t, nullptr, B, height, width, plan, eps_out, workspace, workspace_bytes,
+                      reinterpret_cast<hipStream_t>(stream), false, nullptr, D, &map, cx);
 } catch (...) { return hedit_abi_catch(); }
 
 // ---- input gradient (unetgrad.h)

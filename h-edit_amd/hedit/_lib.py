@@ -93,6 +93,13 @@ _SIGS = {    "hedit_last_error": (C.c_char_p, []),
                                      C.c_void_p]),
     "hedit_unet_forward_shared": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_void_p, C.c_int,
                                             C.c_int, C.c_int, C.POINTER(P2PPlan), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hedit_unet_context_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "hedit_unet_context_destroy": (None, [C.c_void_p]),
+    "hedit_unet_forward_bound": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int,
+                                           C.c_int, C.POINTER(P2PPlan), C.c_void_p, C.c_void_p, C.c_size_t,
+                                           C.c_void_p]),
+    "hedit_unet_forward_shared_bound": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_float, C.c_void_p, C.c_int,
+                                                  C.c_int, C.c_int, C.POINTER(P2PPlan), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "hedit_unet_create_grad": (C.c_int, [C.POINTER(UnetCfg), C.POINTER(C.c_void_p)]),
     "hedit_unet_grad_workspace_bytes": (C.c_size_t, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "hedit_unet_forward_keep": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,

@@ -73,6 +73,8 @@ class Schedule:
 
 
 class HEditEngine:
+    _bind_contexts = True     # run(): project each context row set once (UNetContext); False: hand every call the tensors (tests)
+
     def __init__(self, model, share_latents=True):
         self.model = model
         # The sampler's UNet calls evaluate each latent under several contexts.  True: such a call hands the executor the
@@ -290,6 +292,18 @@ class HEditEngine:
 
         share = self.share_latents
 
+        # The context rows are fixed over the loop: each row set the loop uses is projected once (a UNetContext, made at its
+        # first use and dropped on return) instead of in every call.  A foreign controller's calls keep the tensors.
+        row_sets = {"base4": ctx_base4, "base2": ctx_base2, "edit": ctx_edit, "src": ctx_src, "edit5": ctx_edit5}
+        bound = {}
+
+        def rows_of(name):
+            if foreign or not self._bind_contexts:
+                return row_sets[name]
+            if name not in bound:
+                bound[name] = self.unet.make_context(row_sets[name])
+            return bound[name]
+
         def unet_rows(parts, blocks, t, ctx_rows, plan=None):
             """One UNet call on the rows torch.cat([parts[b] for b in blocks]); every part is n latents."""
             if not share:
@@ -303,80 +317,84 @@ class HEditEngine:
                 return self.unet.forward_hooked(torch.cat([parts[b] for b in blocks]), t, ctx_edit, controller, save)
             # controller=None: the reference's processors then leave every attention map alone (ptp_utils.py:98-101)
             plan = controller._plan(self.unet, rows, xT.shape[2], xT.shape[3], save) if controller is not None else None
-            e = unet_rows(parts, blocks, t, ctx_edit5 if rows == 5 * n else ctx_edit, plan)
+            e = unet_rows(parts, blocks, t, rows_of("edit5" if rows == 5 * n else "edit"), plan)
             if controller is not None:
                 controller._after_pass(save)
             return e
 
-        carry = None      # (eps(x_orig, t, null), eps(x_orig, t, src)) from the previous P2P pass
-        reuse = reuse_orig_eps and p2p and implicit
-        for i, t in enumerate(op):
-            idx = T - i - (T - after_skip_steps + 1)
-            z = zs[idx] if zs is not None else None
-            tt = op[i + 1] if i < len(op) - 1 else 0
-            eta_i = float(eta[idx]) if isinstance(eta, (list, tuple)) else float(eta)   # etas[idx], p2p_h_edit.py:619,665
-            coef = S.step_coef(t, tt, eta_i, ddim_inv, cfg_scales, w_rec)
+        try:
+            carry = None      # (eps(x_orig, t, null), eps(x_orig, t, src)) from the previous P2P pass
+            reuse = reuse_orig_eps and p2p and implicit
+            for i, t in enumerate(op):
+                idx = T - i - (T - after_skip_steps + 1)
+                z = zs[idx] if zs is not None else None
+                tt = op[i + 1] if i < len(op) - 1 else 0
+                eta_i = float(eta[idx]) if isinstance(eta, (list, tuple)) else float(eta)   # etas[idx], p2p_h_edit.py:619,665
+                coef = S.step_coef(t, tt, eta_i, ddim_inv, cfg_scales, w_rec)
 
-            if (not p2p) and implicit and i == 0 and ahead != -1:
-                # one extra correction of the start sample when steps were skipped (p2p_h_edit.py:239-267)
-                xe = xt[n:]
-                e = unet_rows([xe], (0, 0, 0, 0), t, ctx_edit, off)
-                c0 = S.step_coef(t, tt, eta_i, ddim_inv, cfg_scales, w_rec, coeff=S.edit_coeff(ahead, t, eta_i, ddim_inv))
-                new = torch.empty_like(xe)
-                self.step_update(e[0:n], e[2 * n:3 * n], e[n:2 * n], e[3 * n:], xe, xe, new, n, False, c0)
-                xt = torch.cat([xt[:n], new]).contiguous()
+                if (not p2p) and implicit and i == 0 and ahead != -1:
+                    # one extra correction of the start sample when steps were skipped (p2p_h_edit.py:239-267)
+                    xe = xt[n:]
+                    e = unet_rows([xe], (0, 0, 0, 0), t, rows_of("edit"), off)
+                    c0 = S.step_coef(t, tt, eta_i, ddim_inv, cfg_scales, w_rec, coeff=S.edit_coeff(ahead, t, eta_i, ddim_inv))
+                    new = torch.empty_like(xe)
+                    self.step_update(e[0:n], e[2 * n:3 * n], e[n:2 * n], e[3 * n:], xe, xe, new, n, False, c0)
+                    xt = torch.cat([xt[:n], new]).contiguous()
 
-            # ---- base pass -> x_{t-1}^orig, x_{t-1}^base
-            if p2p and reuse and carry is not None:
-                e2 = unet_rows([xt[n:]], (0, 0), t, ctx_base2, off)
-                e = torch.cat([carry[0], e2[:n], carry[1], e2[n:]])
-                self.step_base(e, xt, z, x_prev, n, 4, coef)
-            elif p2p:
-                e = unet_rows([xt[:n], xt[n:]], (0, 1, 0, 1), t, ctx_base4, off)
-                self.step_base(e, xt, z, x_prev, n, 4, coef)
-            else:
-                e = unet_rows([xt[n:]], (0, 0), t, ctx_base2, off)
-                self.step_base(e, xt, z, x_prev, n, 2, coef)
-            x_orig, x_base = x_prev[:n], x_prev[n:]
-
-            if not implicit:
-                new = torch.empty_like(x_base)
-                if p2p:
-                    e_src = self.unet.forward_raw(xt[n:].contiguous(), t, ctx_src, off)
-                    e = p2p_pass([xt[:n], xt[n:]], (0, 1, 0, 1), t, True)
-                    self.step_update(e[n:2 * n], e_src, e[n:2 * n], e[3 * n:], x_base, x_base, new, n, False, coef)
+                # ---- base pass -> x_{t-1}^orig, x_{t-1}^base
+                if p2p and reuse and carry is not None:
+                    e2 = unet_rows([xt[n:]], (0, 0), t, rows_of("base2"), off)
+                    e = torch.cat([carry[0], e2[:n], carry[1], e2[n:]])
+                    self.step_base(e, xt, z, x_prev, n, 4, coef)
+                elif p2p:
+                    e = unet_rows([xt[:n], xt[n:]], (0, 1, 0, 1), t, rows_of("base4"), off)
+                    self.step_base(e, xt, z, x_prev, n, 4, coef)
                 else:
-                    e = unet_rows([xt[n:]], (0, 0, 0, 0), t, ctx_edit, off)
-                    self.step_update(e[0:n], e[2 * n:3 * n], e[n:2 * n], e[3 * n:], x_base, x_base, new, n, False, coef)
-                x_k = new
-            else:
-                x_k = x_base.clone()
-                for k in range(K):
-                    new = torch.empty_like(x_k)
-                    if p2p:
-                        save = not (k < K - 1 and K > 1)
-                        if fuse_src_pass:
-                            e = p2p_pass([x_orig, x_k], (0, 1, 0, 1, 1), tt, save)
-                            e_src = e[4 * n:]
-                        else:
-                            e_src = self.unet.forward_raw(x_k, tt, ctx_src, off)
-                            e = p2p_pass([x_orig, x_k], (0, 1, 0, 1), tt, save)
-                        self.step_update(e[n:2 * n], e_src, e[n:2 * n], e[3 * n:4 * n], x_k, x_base, new, n,
-                                         k > 0 and style is None and rec_pull, coef)
-                        if style is not None and style[0] is not None:
-                            with torch.enable_grad():
-                                new = self.style_step(e[n:2 * n], e_src, e[n:2 * n], e[3 * n:4 * n], new, tt, cfg_scales,
-                                                      style[0], style[1])
-                        if reuse:
-                            carry = (e[0:n], e[2 * n:3 * n])
-                    else:
-                        e = unet_rows([x_k], (0, 0, 0, 0), tt, ctx_edit, off)
-                        self.step_update(e[0:n], e[2 * n:3 * n], e[n:2 * n], e[3 * n:], x_k, x_base, new, n, k > 0, coef)
-                    x_k = new
+                    e = unet_rows([xt[n:]], (0, 0), t, rows_of("base2"), off)
+                    self.step_base(e, xt, z, x_prev, n, 2, coef)
+                x_orig, x_base = x_prev[:n], x_prev[n:]
 
-            xt = torch.cat([x_orig, x_k]).contiguous()
-            if step_cb is not None:
-                xt = step_cb(xt)
+                if not implicit:
+                    new = torch.empty_like(x_base)
+                    if p2p:
+                        e_src = self.unet.forward_raw(xt[n:].contiguous(), t, rows_of("src"), off)
+                        e = p2p_pass([xt[:n], xt[n:]], (0, 1, 0, 1), t, True)
+                        self.step_update(e[n:2 * n], e_src, e[n:2 * n], e[3 * n:], x_base, x_base, new, n, False, coef)
+                    else:
+                        e = unet_rows([xt[n:]], (0, 0, 0, 0), t, rows_of("edit"), off)
+                        self.step_update(e[0:n], e[2 * n:3 * n], e[n:2 * n], e[3 * n:], x_base, x_base, new, n, False, coef)
+                    x_k = new
+                else:
+                    x_k = x_base.clone()
+                    for k in range(K):
+                        new = torch.empty_like(x_k)
+                        if p2p:
+                            save = not (k < K - 1 and K > 1)
+                            if fuse_src_pass:
+                                e = p2p_pass([x_orig, x_k], (0, 1, 0, 1, 1), tt, save)
+                                e_src = e[4 * n:]
+                            else:
+                                e_src = self.unet.forward_raw(x_k, tt, rows_of("src"), off)
+                                e = p2p_pass([x_orig, x_k], (0, 1, 0, 1), tt, save)
+                            self.step_update(e[n:2 * n], e_src, e[n:2 * n], e[3 * n:4 * n], x_k, x_base, new, n,
+                                             k > 0 and style is None and rec_pull, coef)
+                            if style is not None and style[0] is not None:
+                                with torch.enable_grad():
+                                    new = self.style_step(e[n:2 * n], e_src, e[n:2 * n], e[3 * n:4 * n], new, tt, cfg_scales,
+                                                          style[0], style[1])
+                            if reuse:
+                                carry = (e[0:n], e[2 * n:3 * n])
+                        else:
+                            e = unet_rows([x_k], (0, 0, 0, 0), tt, rows_of("edit"), off)
+                            self.step_update(e[0:n], e[2 * n:3 * n], e[n:2 * n], e[3 * n:], x_k, x_base, new, n, k > 0, coef)
+                        x_k = new
+
+                xt = torch.cat([x_orig, x_k]).contiguous()
+                if step_cb is not None:
+                    xt = step_cb(xt)
+        finally:
+            for cx in bound.values():
+                cx.close()
         return xt[n:].clone(), xt[:n].clone()
 
     # ------------------------------------------------------------------ Plug-and-Play loop

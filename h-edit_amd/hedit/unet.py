@@ -32,6 +32,7 @@ import math
 import torch
 
 from . import _lib
+from . import native
 from .native import NativeOwner
 
 SD15_CONFIG = dict(in_channels=4, out_channels=4, sample_size=64,
@@ -116,6 +117,30 @@ class _EpsGrad(torch.autograd.Function):
             elif want_x:
                 _lib.check(m._lib.hedit_unet_backward(m._h, _lib.ptr(g), _lib.ptr(dx), _lib.ptr(m._gws), _lib.cur_stream()))
         return dx, dc, None, None
+
+
+class UNetContext(NativeOwner):
+    """A bound text context (hedit_unet_context, include/hedit.h): the padded bf16 rows of ``ctx`` and their attn2 key / value
+    projections for every transformer block, computed once by ``UNet2DConditionModel.make_context`` and handed to
+    ``forward_raw(ctx=...)`` in place of the tensor.  A SNAPSHOT: later changes to the tensor (or to the model's weights) do not
+    reach it.  Owns device memory of its own (4 MB per row for SD-1.5); ``close()`` or dropping the object frees it, before or
+    after the model."""
+    _family, _finalizes = "unet_context", False
+
+    def __init__(self, model, ctx):
+        rows, _, dim = ctx.shape
+        if ctx.dtype != torch.float32 or ctx.shape != (rows, 77, model.config["cross_attention_dim"]):
+            raise ValueError(f"the context rows must be float32 (B, 77, {model.config['cross_attention_dim']}), got "
+                             f"{ctx.dtype} {tuple(ctx.shape)}")
+        ctx = ctx.detach().to(model.device).contiguous()
+        lib, h = model._lib, C.c_void_p()
+        with native._device_ctx(model.device):
+            _lib.check(lib.hedit_unet_context_create(model._h, _lib.ptr(ctx), rows, _lib.cur_stream(), C.byref(h)))
+            native._sync_stream()      # the launches read `ctx`: keep it alive until they ran
+        self.rows = rows
+        self._h, self._lib, self._h_device = h, lib, model.device
+
+    close = NativeOwner._native_release
 
 
 class UNet2DConditionModel(NativeOwner):
@@ -273,34 +298,48 @@ class UNet2DConditionModel(NativeOwner):
         return rows[:n.value]
 
     # ---------------------------------------------------------------- forward
+    def make_context(self, ctx_rows):
+        """ctx_rows fp32 (B,77,D) -> a UNetContext for ``forward_raw(ctx=...)``: the per-call context projections, once"""
+        return UNetContext(self, ctx_rows)
+
     def forward_raw(self, sample, t, ctx, plan=None, out=None, row_latent=None):
-        """sample fp32 (B,C,H,W) cuda, t python float, ctx fp32 (B,77,D) cuda, plan: _lib.P2PPlan.
+        """sample fp32 (B,C,H,W) cuda, t python float, ctx fp32 (B,77,D) cuda or a UNetContext of B rows (make_context: the
+        same bits without the per-call projections), plan: _lib.P2PPlan.
         row_latent (sequence of B ints): ``sample`` then holds only the DISTINCT latents and row r evaluates
         ``sample[row_latent[r]]`` under ``ctx[r]`` -- the bits of the call on ``sample[row_latent]``, with the part of the
         network in front of the first cross-attention run once per latent where the executor may (hedit_unet_forward_shared)."""
         B, Cc, H, W = sample.shape
         if row_latent is not None:
             B = len(row_latent)
-        if sample.dtype != torch.float32 or ctx.dtype != torch.float32:
+        bound = isinstance(ctx, UNetContext)
+        if sample.dtype != torch.float32 or (not bound and ctx.dtype != torch.float32):
             raise TypeError("sample and encoder_hidden_states must be float32")
-        if ctx.shape != (B, 77, self.config["cross_attention_dim"]):
-            raise ValueError(f"encoder_hidden_states must be ({B}, 77, {self.config['cross_attention_dim']}), "
-                             f"got {tuple(ctx.shape)}")
+        if bound:
+            if ctx._h is None:
+                raise _lib.HipError("the UNetContext was closed")
+            ctx_arg = ctx._h
+        else:
+            if ctx.shape != (B, 77, self.config["cross_attention_dim"]):
+                raise ValueError(f"encoder_hidden_states must be ({B}, 77, {self.config['cross_attention_dim']}), "
+                                 f"got {tuple(ctx.shape)}")
+            ctx = ctx.contiguous()
+            ctx_arg = _lib.ptr(ctx)
         sample = sample.contiguous()
-        ctx = ctx.contiguous()
         if out is None:
             out = torch.empty(B, self.config["out_channels"], H, W, dtype=torch.float32, device=sample.device)
         ws = self._workspace(B, H, W)
         if row_latent is None:
-            _lib.check(self._lib.hedit_unet_forward(
-                self._h, _lib.ptr(sample), C.c_float(float(t)), _lib.ptr(ctx), B, H, W,
+            fwd = self._lib.hedit_unet_forward_bound if bound else self._lib.hedit_unet_forward
+            _lib.check(fwd(
+                self._h, _lib.ptr(sample), C.c_float(float(t)), ctx_arg, B, H, W,
                 C.byref(plan) if plan is not None else None, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
                 _lib.cur_stream()))
             return out
         if sample.data_ptr() % 16:
             sample = sample.clone()
-        _lib.check(self._lib.hedit_unet_forward_shared(
-            self._h, _lib.ptr(sample), sample.shape[0], (C.c_int * B)(*row_latent), C.c_float(float(t)), _lib.ptr(ctx), B, H, W,
+        fwd = self._lib.hedit_unet_forward_shared_bound if bound else self._lib.hedit_unet_forward_shared
+        _lib.check(fwd(
+            self._h, _lib.ptr(sample), sample.shape[0], (C.c_int * B)(*row_latent), C.c_float(float(t)), ctx_arg, B, H, W,
             C.byref(plan) if plan is not None else None, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
             _lib.cur_stream()))
         return out

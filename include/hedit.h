@@ -155,6 +155,28 @@ int hedit_unet_forward(hedit_unet* h, const float* x, float t, const float* ctx,
 int hedit_unet_forward_shared(hedit_unet* h, const float* x, int D, const int* row_latent, float t, const float* ctx, int B,
                               int height, int width, const hedit_p2p_plan* plan, float* eps_out, void* workspace,
                               size_t workspace_bytes, void* stream);
+/* A bound text context.  The context rows of an edit are fixed over its sampling steps, while hedit_unet_forward starts every call
+ * by padding them to bf16 [B * 80][ctx_dim] and projecting them onto the stacked attn2 key / value matrices of all transformer
+ * blocks (two GEMMs: 368 GFLOP at 120 rows of SD-1.5).  hedit_unet_context_create runs exactly those three launches once, on
+ * `stream`, for ctx fp32 [B][77][ctx_dim], into device memory the object owns (allocated here, never inside a forward:
+ * 2 * B * 80 * (ctx_n + ctx_dim / 2) * 2 bytes, 4 MB per row and 0.48 GB at 120 rows for SD-1.5; HEDIT_ERR_STATE while `stream`
+ * is capturing, HEDIT_ERR_HIP when the memory is not to be had).  hedit_unet_forward_bound / hedit_unet_forward_shared_bound are
+ * hedit_unet_forward / hedit_unet_forward_shared with the object in place of `ctx`: they skip the three launches, read the
+ * object's buffers, and give the same bits.  hedit_unet_workspace_bytes(h, B, ..) is enough for either form.
+ * Contract: the object is a SNAPSHOT of the rows and of the handle's weights at create time.  Changing the fp32 tensor, or
+ * loading parameters, afterwards does not change it; nothing compares pointers to guess whether a tensor is "the same".  A call
+ * with another B than the object was created for, or with an object of another handle, returns HEDIT_ERR_ARG, and so does a call
+ * while an attention hook is set (the hook path, hedit_unet_forward_keep, _vjp and _backward_ctx take the fp32 rows).  The calls
+ * that read the object must be ordered after its creation (the same stream, or an event).  hedit_unet_context_destroy waits for
+ * the device, accepts NULL, and may run before or after hedit_unet_destroy of the handle. */
+typedef struct hedit_unet_context hedit_unet_context;
+int hedit_unet_context_create(hedit_unet* h, const float* ctx, int B, void* stream, hedit_unet_context** out);
+void hedit_unet_context_destroy(hedit_unet_context* cx);
+int hedit_unet_forward_bound(hedit_unet* h, const float* x, float t, const hedit_unet_context* cx, int B, int height, int width,
+                             const hedit_p2p_plan* plan, float* eps_out, void* workspace, size_t workspace_bytes, void* stream);
+int hedit_unet_forward_shared_bound(hedit_unet* h, const float* x, int D, const int* row_latent, float t,
+                                    const hedit_unet_context* cx, int B, int height, int width, const hedit_p2p_plan* plan,
+                                    float* eps_out, void* workspace, size_t workspace_bytes, void* stream);
 /* Host-language attention controller -- the reference's hook point, text-guided/p2p/ptp_utils.py:98-106
  * (`self.controller(attention_probs, is_cross, self.place_in_unet, save_attn)` between the softmax and the product with V).
  * With a hook set, every attention layer of hedit_unet_forward writes its probabilities to HBM as fp32
@@ -437,7 +459,11 @@ int hedit_storage_is_f16(void);
  *        compares the two on one library.
  * bit 3: gemm launches that would run a persistent kernel (csrc/pgemm.hip, csrc/pconv.hip) run the one-shot igemm_kernel of the
  *        same tile instead -- the same bits by construction; tools/pgemm_ab.py / tools/pconv_ab.py compare them (torch.equal)
- *        and time both on one box. */
+ *        and time both on one box.
+ * bit 4: the one-launch GroupNorm of images below 32 x 32 (csrc/norm.hip) launches its kept first form, gn_small_narrow_kernel
+ *        (4 bytes per lane, grid (group, image)), instead of gn_small_kernel (wide vectors through LDS, the groups of an image on
+ *        one XCD) -- the same bits by construction; tests/test_gpu_gn_small_bits.py compares them (torch.equal) and
+ *        tools/gn_small_bench.py times both on one box. */
 int hedit_test_set_flags(int flags);
 size_t hedit_k_groupnorm_ws_bytes(int B, int HW, int C);
 int hedit_k_groupnorm_affine(const void* x, const float* gamma, const float* beta, int B, int HW, int C, int G, float eps, void* ws,
