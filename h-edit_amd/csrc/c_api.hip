@@ -10,6 +10,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "pnet.h"
 
 static thread_local std::string g_last_error;
 void hedit_set_error(const std::string& msg) { g_last_error = msg; }
@@ -577,6 +578,215 @@ int hedit_k_pack_linear_t(const float* w, void* out, int O, int I, void* stream)
 int hedit_k_flip_oihw(const float* w, float* out, int O, int I, int k, void* stream) try {
   ARG_CHECK(w && out, "flip args");
   return flip_oihw_launch(w, out, O, I, k, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+// ---- single kernels (parity tests), precise family: pnet.hip / encoder.hip launchers and one layer as the executors run it (pnet.h)
+int hedit_k_split3_geometry(int C, int* Cs, int* Kp) try {
+  ARG_CHECK(C >= 1 && Cs && Kp, "split3_geometry args");
+  *Cs = split_cs(C);
+  *Kp = split_kp(C);
+  return HEDIT_OK;
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_split3(const float* x, int ldx, const float* z, const float* p, const float* q, int pq_img, int op, void* out, int Kp, int Cs,
+                   int C, int geo, int B, int H, int W, int worder, int64_t rows_out, void* stream) try {
+  ARG_CHECK(x && out && rows_out >= 1 && ldx >= C && geo >= 0 && geo <= 2 && op >= P_COPY && op <= P_GELU, "split3 args");
+  ARG_CHECK(geo != 1 || (H % 2 == 0 && W % 2 == 0), "split3: geo 1 needs even H and W");
+  Split3Params s{};
+  s.x = x; s.ldx = ldx; s.z = z; s.p = p; s.q = q; s.pq_img = pq_img; s.op = op;
+  s.out = reinterpret_cast<bf16_t*>(out); s.Kp = Kp; s.Cs = Cs; s.C = C; s.geo = geo; s.B = B; s.H = H; s.W = W; s.worder = worder;
+  return split3_launch(s, (long)rows_out, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_pack_split3_w(const float* w, const float* scale, void* out, int O, int I, int k, int dgrad, int Cs, int Kp, int rows_out,
+                          int perm_hw, int perm_c, void* stream) try {
+  ARG_CHECK(w && out && O >= 1 && I >= 1 && (k == 1 || k == 3) && rows_out >= (dgrad ? I : O), "pack_split3_w args");
+  return pack_split3_w_launch(w, scale, reinterpret_cast<bf16_t*>(out), O, I, k, dgrad, Cs, Kp, rows_out, perm_hw, perm_c, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+// op_split + pgemm of pnet.h on an arena over ws; the weight is packed as make_pconv packs the side that is used
+static int precise_conv_run(const float* x, int op, const float* p, const float* q, int pq_img, const float* z, int geo, const float* w,
+                            const float* scale, int O, int I, int k, int perm_hw, int perm_c, int dgrad, int mode, int B, int Hin, int Win,
+                            float* out, int* chunk_kt, int* splits, void* ws, size_t ws_bytes, hipStream_t st, bool dry, size_t* peak) {
+  ARG_CHECK(O >= 1 && I >= 1 && B >= 1 && Hin >= 1 && Win >= 1 && geo >= 0 && geo <= 2 && mode >= 0 && mode <= 2, "precise_conv shape");
+  ARG_CHECK(k == (mode == 0 ? 1 : 3), "precise_conv: k = 1 with mode 0, 3 with the convolution modes");
+  ARG_CHECK(geo != 1 || (Hin % 2 == 0 && Win % 2 == 0), "precise_conv: geo 1 needs even H and W");
+  const int Hs = geo == 1 ? Hin / 2 : (geo == 2 ? Hin * 2 : Hin), Ws = geo == 1 ? Win / 2 : (geo == 2 ? Win * 2 : Win);
+  ARG_CHECK(mode != 2 || (Hs % 2 == 0 && Ws % 2 == 0), "precise_conv: mode 2 needs an even image");
+  PF f{B, st, Arena{}};
+  f.ar.dry = dry;
+  f.ar.base = reinterpret_cast<char*>(ws);
+  f.ar.cap = ws_bytes;
+  const int Cin = dgrad ? O : I;
+  PConv c;
+  c.O = O; c.I = I; c.k = k;
+  c.rows_f = (O + 3) / 4 * 4;
+  c.rows_b = (I + 3) / 4 * 4;
+  const int rows = dgrad ? c.rows_b : c.rows_f;
+  bf16_t *wp, *A;
+  TRY(aalloc(f, &wp, (size_t)rows * k * k * split_kp(Cin)));
+  if (!dry) TRY(pack_split3_w_launch(w, scale, wp, O, I, k, dgrad, split_cs(Cin), split_kp(Cin), rows, perm_hw, perm_c, st));
+  (dgrad ? c.wb : c.wf) = wp;
+  TRY(op_split(f, x, Cin, op, p, q, pq_img, z, geo, Hin, Win, (long)B * Hin * Win, &A));
+  const long M = (long)B * Hs * Ws / (mode == 2 ? 4 : 1);
+  float* o;
+  TRY(pgemm(f, A, c, dgrad != 0, mode, Hs, Ws, M, &o));
+  const int K = (mode == 0 ? 1 : 9) * split_kp(Cin);
+  const int ck = gemm_canonical_chunk((int)(M / B) * GEMM_NOMINAL_BATCH, rows, K);
+  if (chunk_kt) *chunk_kt = ck;
+  if (splits) *splits = gemm_plan_splits((int)M, rows, K, ck);
+  if (!dry) HIP_TRY(hipMemcpyAsync(out, o, (size_t)M * rows * sizeof(float), hipMemcpyDeviceToDevice, st));
+  if (peak) *peak = f.ar.peak;
+  return HEDIT_OK;
+}
+
+size_t hedit_k_precise_conv_ws_bytes(int O, int I, int k, int dgrad, int mode, int geo, int B, int Hin, int Win) try {
+  size_t peak = 0;
+  const int rc = precise_conv_run(nullptr, P_COPY, nullptr, nullptr, 0, nullptr, geo, nullptr, nullptr, O, I, k, 0, 0, dgrad, mode, B, Hin, Win,
+                                  nullptr, nullptr, nullptr, nullptr, 0, nullptr, true, &peak);
+  return dry_run_bytes(rc, peak);
+} catch (...) { (void)hedit_abi_catch(); return 0; }
+
+int hedit_k_precise_conv(const float* x, int op, const float* p, const float* q, int pq_img, const float* z, int geo, const float* w_oihw,
+                         const float* scale, int O, int I, int k, int perm_hw, int perm_c, int dgrad, int mode, int B, int Hin, int Win,
+                         float* out, int* chunk_kt, int* splits, void* ws, size_t ws_bytes, void* stream) try {
+  ARG_CHECK(x && w_oihw && out && ws, "precise_conv args");
+  ARG_CHECK(reinterpret_cast<uintptr_t>(ws) % 256 == 0, "precise_conv: the workspace must be 256-byte aligned");
+  TRY(gemm_prepare());
+  return precise_conv_run(x, op, p, q, pq_img, z, geo, w_oihw, scale, O, I, k, perm_hw, perm_c, dgrad, mode, B, Hin, Win, out, chunk_kt,
+                          splits, ws, ws_bytes, S(stream), false, nullptr);
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_bn_affine(const float* g, const float* b, const float* m, const float* v, float eps, float* p, float* q, int C, int rep,
+                      void* stream) try {
+  ARG_CHECK(g && b && m && v && p && q && C >= 1 && rep >= 1, "bn_affine args");
+  return bn_affine_launch(g, b, m, v, eps, p, q, C, rep, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_bn_fold_bias(const float* bias, const float* g, const float* b, const float* m, const float* v, float eps, float* p, float* q,
+                         int C, void* stream) try {
+  ARG_CHECK(g && b && m && v && p && q && C >= 1, "bn_fold_bias args");
+  return bn_fold_bias_launch(bias, g, b, m, v, eps, p, q, C, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_act(const float* x, const float* p, const float* q, float* y, int64_t total, int C, int op, void* stream) try {
+  ARG_CHECK(x && y && total >= 1 && C >= 1 && ((op == P_PRELU && p) || op == P_RELU), "act args");
+  return act_launch(x, p, q, y, (long)total, C, op, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_se_nslab(int HW) { return se_nslab(HW); }
+
+int hedit_k_se_pool(const float* u, float* part, int B, int HW, int C, void* stream) try {
+  ARG_CHECK(u && part && B >= 1 && HW >= 1 && C >= 1, "se_pool args");
+  return se_pool_launch(u, part, B, HW, C, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_se_fc(const float* part, const float* bias, const float* w1, const float* w2, float* hbuf, float* sbuf, int B, int HW, int C,
+                  int R, void* stream) try {
+  ARG_CHECK(part && bias && w1 && w2 && hbuf && sbuf && B >= 1 && HW >= 1, "se_fc args");
+  return se_fc_launch(part, bias, w1, w2, hbuf, sbuf, B, HW, C, R, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_se_combine(const float* u, const float* bias, const float* s, const float* sc, const float* sc_bias, const float* X, int stride,
+                       float* Y, int B, int Ho, int Wo, int C, void* stream) try {
+  ARG_CHECK(u && bias && s && Y && (sc ? sc_bias != nullptr : X != nullptr) && stride >= 1, "se_combine args");
+  return se_combine_launch(u, bias, s, sc, sc_bias, X, stride, Y, B, Ho, Wo, C, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_se_bwd_reduce(const float* dY, const float* u, const float* bias, float* part, int B, int HW, int C, void* stream) try {
+  ARG_CHECK(dY && u && bias && part && B >= 1 && HW >= 1 && C >= 1, "se_bwd_reduce args");
+  return se_bwd_reduce_launch(dY, u, bias, part, B, HW, C, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_se_fc_bwd(const float* part, const float* sbuf, const float* hbuf, const float* w1, const float* w2, float* rbuf, int B, int C,
+                      int R, int HW, void* stream) try {
+  ARG_CHECK(part && sbuf && hbuf && w1 && w2 && rbuf && B >= 1 && HW >= 1, "se_fc_bwd args");
+  return se_fc_bwd_launch(part, sbuf, hbuf, w1, w2, rbuf, B, C, R, HW, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_unit_bwd_combine(const float* dxa, const float* p, const float* dsc, int stride, float* dX, int B, int H, int W, int C,
+                             void* stream) try {
+  ARG_CHECK(dxa && p && dsc && dX && stride >= 1 && H % stride == 0 && W % stride == 0, "unit_bwd_combine args");
+  return unit_bwd_combine_launch(dxa, p, dsc, stride, dX, B, H, W, C, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_scale_cols(const float* x, const float* p, float* y, int64_t total, int n, void* stream) try {
+  ARG_CHECK(x && p && y && total >= 1 && n >= 1, "scale_cols args");
+  return scale_cols_launch(x, p, y, (long)total, n, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_face_pool(const float* img, float* out, int B, void* stream) try {
+  ARG_CHECK(img && out && B >= 1, "face_pool args");
+  return face_pool_launch(img, out, B, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_face_pool_bwd(const float* g, int ldg, float* dimg, int B, void* stream) try {
+  ARG_CHECK(g && dimg && ldg >= 3 && B >= 1, "face_pool_bwd args");
+  return face_pool_bwd_launch(g, ldg, dimg, B, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_cos_head(const float* raw, const float* bias, const float* ref, int ref_stride, float* feat, float* loss, float* df, int B,
+                     int D, float scale, void* stream) try {
+  ARG_CHECK(raw && bias && B >= 1 && D >= 1, "cos_head args");
+  return cos_head_launch(raw, bias, ref, ref_stride, feat, loss, df, B, D, scale, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_lpips_prep(const float* img, float* out, const float* shift3, const float* scale3, int B, int H, int W, void* stream) try {
+  ARG_CHECK(img && out && shift3 && scale3, "lpips_prep args");
+  return lpips_prep_launch(img, out, shift3, scale3, B, H, W, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_lpips_prep_bwd(const float* g, int ldg, float* dimg, const float* scale3, int B, int H, int W, void* stream) try {
+  ARG_CHECK(g && dimg && scale3 && ldg >= 3, "lpips_prep_bwd args");
+  return lpips_prep_bwd_launch(g, ldg, dimg, scale3, B, H, W, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_maxpool2(const float* z, float* zp, uint8_t* idx, int B, int H, int W, int C, void* stream) try {
+  ARG_CHECK(z && zp && idx, "maxpool2 args");
+  return maxpool2_launch(z, zp, idx, B, H, W, C, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_maxpool2_bwd(const float* gp, const uint8_t* idx, const float* add, float* G, int B, int H, int W, int C, void* stream) try {
+  ARG_CHECK(gp && idx && G && H % 2 == 0 && W % 2 == 0, "maxpool2_bwd args");
+  return maxpool2_bwd_launch(gp, idx, add, G, B, H, W, C, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_lpips_head(const float* z, const float* bias, const float* src, int64_t src_img_stride, const float* w, float* fn_out,
+                       float* dpix, float* dF, int B, int HW, int C, float gscale, void* stream) try {
+  ARG_CHECK(z && bias && (src ? (w && dpix) : fn_out != nullptr), "lpips_head args");
+  return lpips_head_launch(z, bias, src, (long)src_img_stride, w, fn_out, dpix, dF, B, HW, C, gscale, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_lpips_reduce(const float* dpix, float* acc, int B, int HW, int first, void* stream) try {
+  ARG_CHECK(dpix && acc && B >= 1 && HW >= 1, "lpips_reduce args");
+  return lpips_reduce_launch(dpix, acc, B, HW, first, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_enc_patchify(const float* img, float* X, int B, int R, int p, int bwd, void* stream) try {
+  ARG_CHECK(img && X && B >= 1 && p >= 1 && R >= p && R % p == 0, "enc_patchify args");
+  return enc_patchify_launch(img, X, B, R, p, bwd, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_enc_tokens(const float* E, const float* cbias, const float* cls, const float* pos, float* T, int B, int L, int W,
+                       void* stream) try {
+  ARG_CHECK(E && cls && pos && T && B >= 1 && L >= 2 && W >= 1, "enc_tokens args");
+  return enc_tokens_launch(E, cbias, cls, pos, T, B, L, W, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_enc_gather_rows(const float* T, const int32_t* idx, float* R, int B, int L, int W, void* stream) try {
+  ARG_CHECK(T && R && B >= 1 && L >= 1 && W >= 1, "enc_gather_rows args");
+  return enc_gather_rows_launch(T, idx, R, B, L, W, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_enc_ln(const float* x, const float* g, const float* b, float* y, float* stats, int64_t rows, int W, float eps,
+                   void* stream) try {
+  ARG_CHECK(x && g && b && y && rows >= 1 && W >= 1, "enc_ln args");
+  return enc_ln_launch(x, g, b, y, stats, (long)rows, W, eps, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_enc_add_bias_res(const float* raw, const float* bias, const float* res, float* out, int64_t total, int W, void* stream) try {
+  ARG_CHECK(raw && bias && out && total >= 1 && W >= 1, "enc_add_bias_res args");
+  return enc_add_bias_res_launch(raw, bias, res, out, (long)total, W, S(stream));
 } catch (...) { return hedit_abi_catch(); }
 
 }  // extern "C"

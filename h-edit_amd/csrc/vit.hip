@@ -576,4 +576,54 @@ int hedit_vit_gram_fwd_bwd(hedit_vit* h, const float* image, const float* gram_r
              false, true, nullptr);
 } catch (...) { return hedit_abi_catch(); }
 
+// ---- single kernels (parity tests, include/hedit.h): this file's own kernels with the executor's launch geometry
+int hedit_k_vit_ln_bwd(const float* x, const float* dy, const float* g, const float* stats, const float* add, float* dx, int64_t rows, int W,
+                       void* stream) try {
+  ARG_CHECK(x && dy && g && stats && dx && rows >= 1 && W >= 1, "vit_ln_bwd args");
+  hipLaunchKernelGGL(ln_bwd_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), x, dy, g, stats, add, dx,
+                     (long)rows, W);
+  LAUNCH_CHECK();
+  return HEDIT_OK;
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_vit_attn_fwd(const float* qkv, const float* bias, float* A, float* lse, int B, int L, int heads, int slices, void* stream) try {
+  ARG_CHECK(qkv && bias && A && lse && B >= 1 && heads >= 1 && L >= 1 && L <= LMAX && slices >= 0 && slices <= 4, "vit_attn_fwd args");
+  if (int rc = hedit_dyn_lds(reinterpret_cast<const void*>(&attn_fwd_kernel), (int)ATTN_LDS_FWD)) return rc;
+  const int W = heads * HD, z = slices ? slices : attn_slices(heads, B);
+  hipLaunchKernelGGL(attn_fwd_kernel, dim3(heads, B, z), dim3(256), ATTN_LDS_FWD, reinterpret_cast<hipStream_t>(stream), qkv, bias, A, lse, L,
+                     W, 1.0f / sqrtf((float)HD));
+  LAUNCH_CHECK();
+  return HEDIT_OK;
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_vit_attn_bwd(const float* qkv, const float* bias, const float* A, const float* dA, const float* lse, float* dqkv, int B, int L,
+                         int heads, int slices, void* stream) try {
+  ARG_CHECK(qkv && bias && A && dA && lse && dqkv && B >= 1 && heads >= 1 && L >= 1 && L <= LMAX && slices >= 0 && slices <= 4,
+            "vit_attn_bwd args");
+  if (int rc = hedit_dyn_lds(reinterpret_cast<const void*>(&attn_bwd_dq_kernel), (int)ATTN_LDS_DQ)) return rc;
+  if (int rc = hedit_dyn_lds(reinterpret_cast<const void*>(&attn_bwd_dkv_kernel), (int)ATTN_LDS_DKV)) return rc;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int W = heads * HD, z = slices ? slices : attn_slices(heads, B);
+  const float ascale = 1.0f / sqrtf((float)HD);
+  hipLaunchKernelGGL(attn_bwd_dq_kernel, dim3(heads, B, z), dim3(256), ATTN_LDS_DQ, st, qkv, bias, A, dA, lse, dqkv, L, W, ascale);
+  LAUNCH_CHECK();
+  hipLaunchKernelGGL(attn_bwd_dkv_kernel, dim3(heads, B, z), dim3(256), ATTN_LDS_DKV, st, qkv, bias, A, dA, lse, dqkv, L, W, ascale);
+  LAUNCH_CHECK();
+  return HEDIT_OK;
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_vit_drop_cls(const float* dT, float* dE, int B, int L, int W, void* stream) try {
+  ARG_CHECK(dT && dE && B >= 1 && L >= 2 && W >= 1, "vit_drop_cls args");
+  hipLaunchKernelGGL(drop_cls_kernel, egrid((long)B * (L - 1) * W), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), dT, dE, B, L, W);
+  LAUNCH_CHECK();
+  return HEDIT_OK;
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_vit_gram_bwd(const float* FR, const float* nrm, float* dT, int L, int W, float scale, void* stream) try {
+  ARG_CHECK(FR && nrm && dT && L >= 2 && W >= 1, "vit_gram_bwd args");
+  hipLaunchKernelGGL(gram_bwd_kernel, egrid((long)L * W), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), FR, nrm, dT, L, W, scale);
+  LAUNCH_CHECK();
+  return HEDIT_OK;
+} catch (...) { return hedit_abi_catch(); }
+
 }  // extern "C"

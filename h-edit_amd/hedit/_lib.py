@@ -276,6 +276,45 @@ _SIGS = {    "hedit_last_error": (C.c_char_p, []),
     "hedit_k_geglu_bwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "hedit_k_conv3x3_s2_dgrad_pad1": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                                 C.c_void_p]),
+    # single kernels of the precise family (pnet.hip, encoder.hip, vit.hip's gradient kernels)
+    "hedit_k_split3_geometry": (C.c_int, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "hedit_k_split3": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p] + [C.c_int] * 8 +
+                       [C.c_int64, C.c_void_p]),
+    "hedit_k_pack_split3_w": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 9 + [C.c_void_p]),
+    "hedit_k_precise_conv_ws_bytes": (C.c_size_t, [C.c_int] * 9),
+    "hedit_k_precise_conv": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] +
+                             [C.c_int] * 10 + [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "hedit_k_bn_affine": (C.c_int, [C.c_void_p] * 4 + [C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "hedit_k_bn_fold_bias": (C.c_int, [C.c_void_p] * 5 + [C.c_float, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "hedit_k_act": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_int, C.c_void_p]),
+    "hedit_k_se_nslab": (C.c_int, [C.c_int]),
+    "hedit_k_se_pool": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "hedit_k_se_fc": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p]),
+    "hedit_k_se_combine": (C.c_int, [C.c_void_p] * 6 + [C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "hedit_k_se_bwd_reduce": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_void_p]),
+    "hedit_k_se_fc_bwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p]),
+    "hedit_k_unit_bwd_combine": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "hedit_k_scale_cols": (C.c_int, [C.c_void_p] * 3 + [C.c_int64, C.c_int, C.c_void_p]),
+    "hedit_k_face_pool": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "hedit_k_face_pool_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "hedit_k_cos_head": (C.c_int, [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "hedit_k_lpips_prep": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int,
+                                     C.c_void_p]),
+    "hedit_k_lpips_prep_bwd": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "hedit_k_maxpool2": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
+    "hedit_k_maxpool2_bwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+    "hedit_k_lpips_head": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_float, C.c_void_p]),
+    "hedit_k_lpips_reduce": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "hedit_k_enc_patchify": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "hedit_k_enc_tokens": (C.c_int, [C.c_void_p] * 5 + [C.c_int] * 3 + [C.c_void_p]),
+    "hedit_k_enc_gather_rows": (C.c_int, [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
+    "hedit_k_enc_ln": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_int, C.c_float, C.c_void_p]),
+    "hedit_k_enc_add_bias_res": (C.c_int, [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_void_p]),
+    "hedit_k_vit_ln_bwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.c_int, C.c_void_p]),
+    "hedit_k_vit_attn_fwd": (C.c_int, [C.c_void_p] * 4 + [C.c_int] * 4 + [C.c_void_p]),
+    "hedit_k_vit_attn_bwd": (C.c_int, [C.c_void_p] * 6 + [C.c_int] * 4 + [C.c_void_p]),
+    "hedit_k_vit_drop_cls": (C.c_int, [C.c_void_p, C.c_void_p] + [C.c_int] * 3 + [C.c_void_p]),
+    "hedit_k_vit_gram_bwd": (C.c_int, [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

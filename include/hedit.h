@@ -880,6 +880,121 @@ size_t hedit_pixel_metrics_workspace_bytes(int N, int height, int width);
 int hedit_pixel_metrics(const uint8_t* pred, const uint8_t* gt, const uint8_t* mask_pred, const uint8_t* mask_gt, int N, int height,
                         int width, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- single kernels (parity tests), precise family ------------------------------------------------
+ * The kernels of the "precise" path (csrc/pnet.hip, encoder.hip, the attention / LayerNorm gradient kernels of vit.hip) one
+ * by one, for tests/test_gpu_precise_kernels.py.  Thin wrappers: no product kernel and no dispatch is changed by them.  All
+ * pointers are device pointers unless said otherwise; activations are fp32, the split operands bfloat16 in BOTH storage
+ * builds.  Integer ops are the P_* values of csrc/kernels.h: 0 copy, 1 affine p x + q, 2 PReLU, 3 PReLU gradient, 4 ReLU,
+ * 5 ReLU gradient, 6 QuickGELU, 7 QuickGELU gradient, 8 affine + ReLU, 9 exact GELU.
+ *
+ * hedit_k_split3_geometry: the operand geometry of C channels (host pointers): Cs = the stride between the three parts
+ *   (C when 3 C <= 64 or 3 C % 64 == 0, else C rounded up to 64), Kp = 3 Cs rounded up to 64 = the operand's row length.
+ * hedit_k_split3: x fp32 [rows_in][ldx] (ldx >= C) -> out bf16 [rows_out][Kp]: columns [0, C) hi, [Cs, Cs + C) hi,
+ *   [2 Cs, 2 Cs + C) lo of v = op(x) (worder = 1: hi, lo, hi), every other column exact zero.  hi = bf16(v), lo = bf16(v - hi).
+ *   z: the pre-activation of the *_GRAD ops (same geometry and ldx as x), else unused.  p, q [C] (q may be null for the
+ *   activations; both are needed by the affine ops), or [B][C] with pq_img = 1 (affine ops only).  geo 0: rows_out = rows_in;
+ *   geo 1: x is [B][H][W] pixels, out the pixels (2 oy, 2 ox): rows_out = B (H / 2)(W / 2), H and W EVEN (no caller has odd
+ *   ones; an odd size is not supported); geo 2: out is [B][2H][2W], pixel (2 y, 2 x) = pixel (y, x) of x, the others exact
+ *   zero.  B, H, W describe x and are read only with geo != 0 or pq_img.  Eight columns per thread when C % 8 == 0,
+ *   Cs % 8 == 0 and ldx % 4 == 0 (x, z 16-byte aligned), else one: same bits.
+ * hedit_k_pack_split3_w: w fp32 OIHW [O][I][k][k] (k = 1 or 3) -> bf16 [rows_out][k k][Kp], parts (hi, lo, hi) of
+ *   w[o][i][tap] * scale[o] (scale null: 1).  dgrad 0: row o, channel i (Cs, Kp of I, rows_out >= O); dgrad 1: row i,
+ *   channel o, tap k k - 1 - tap (Cs, Kp of O, rows_out >= I).  perm_hw > 0: the input index i of the packed operand counts
+ *   (hw, ch) with ch < perm_c and addresses w's input ch * perm_hw + hw (a Linear behind an NCHW flatten).  Rows beyond the
+ *   real count and every padding column are exact zeros.
+ * hedit_k_precise_conv: one layer as the executors run it (op_split, then pgemm of csrc/pnet.h on an arena over `ws`):
+ *   x fp32 [B * Hin * Win][Cin], Cin = dgrad ? O : I, through hedit_k_split3's op / p / q / pq_img / z / geo (ldx = Cin), times
+ *   the weight packed as above from w_oihw (+ scale, perm_hw, perm_c).  With (Hs, Ws) = the size after geo: mode 0 a linear
+ *   layer over the B Hs Ws rows (k = 1), mode 1 a 3x3 stride-1 pad-1 convolution, mode 2 a 3x3 stride-2 pad-1 one (Hs, Ws
+ *   even).  out fp32 [M][rows], rows = (dgrad ? I : O) rounded up to 4 (the padding columns are exact zeros), M = B Hs Ws
+ *   (mode 2: a quarter).  The summation order is the canonical one of M / B rows per image: *chunk_kt and *splits (host
+ *   pointers, may be null) return gemm_canonical_chunk's and gemm_plan_splits' answers for the launch.  ws: at least
+ *   hedit_k_precise_conv_ws_bytes, 256-byte aligned.
+ *
+ * pnet.hip, one entry per launcher (C = channels, NHWC fp32 activations):
+ *   bn_affine: p[i] = g / sqrt(v + eps), q[i] = b - m p for i < C rep, channel i % C.  bn_fold_bias: p likewise,
+ *     q = (bias - m) p + b (bias null: 0).
+ *   act: y = act(x + q[c]) over `total` elements, op 2 (PReLU, slope p[c]) or 4 (ReLU); q may be null.
+ *   se_nslab(HW): pixel slabs of the SE reductions.  se_pool: part[b][slab][c] = sum over the slab's pixels of u [B][HW][C].
+ *     se_fc: pool = (sum of the slabs in order) / HW + bias; h [B][R] = relu(W1 pool), s [B][C] = sigmoid(W2 h); w1 [R][C],
+ *     w2 [C][R], C <= 512, R <= 32.  se_combine: Y = (u + bias) s[b][c] + shortcut, shortcut = sc + sc_bias (sc given) or
+ *     X [B][Ho stride][Wo stride][C] at (stride y, stride x).  se_bwd_reduce: part[b][slab][c] = sum dY (u + bias).
+ *     se_fc_bwd: r [B][C] = W1^T((W2^T(gs s (1 - s))) [h > 0]) / HW with gs the slab sum.
+ *   unit_bwd_combine: dX [B][H][W][C] = p[c] dxa + (y, x both multiples of stride ? dsc[b][y / stride][x / stride][c] : 0).
+ *   scale_cols: y[i] = x[i] p[i % n].
+ *   face_pool: img [B][3][256][256] -> [B][112][112][3]: adaptive average pool of the crop [35:223, 32:220].  face_pool_bwd:
+ *     g [B 112 112][ldg] (the first three columns) -> dimg [B][3][256][256], zero outside the crop.
+ *   cos_head: f = raw + bias [B][D <= 512]; e = f / |f|; e2 = e / max(|e|, 1e-12) -> feat (or null); with ref
+ *     [B][ref_stride] (ref_stride 0: shared): loss[b] = 1 - <e2, ref>, df = d(scale loss_b) / d raw (either may be null).
+ *   lpips_prep: img [B][3][H][W] -> [B H W][3] = (img - shift_c) / scale_c; lpips_prep_bwd: g [B H W][ldg] -> dimg = g / scale_c.
+ *     shift3, scale3: HOST pointers to three floats.
+ *   maxpool2: z [B][H][W][C] (H, W even) -> zp [B][H/2][W/2][C], idx uint8 = the winner 2 dy + dx (the first of equals).
+ *     maxpool2_bwd: G [B][H][W][C] = add (or 0) + (the pixel won ? gp : 0).
+ *   lpips_head: F = relu(z + bias) [B HW][C <= 512], Fn = F / (|F| + 1e-10).  src null: fn_out = Fn.  Else with src
+ *     [..][HW][C] (image b at src + b src_img_stride, 0 = shared): dpix[pixel] = sum_c w_c (Fn - src)^2 and, if dF is given,
+ *     dF = d(gscale sum_pixels dpix) / dF.
+ *   lpips_reduce: acc[b] (first) = or += mean over the HW pixels of dpix.
+ * encoder.hip: patchify (bwd = 1: X -> img), tokens, gather_rows, ln (stats [rows][2] = (mean, rstd) or null),
+ *   add_bias_res -- the layouts in csrc/kernels.h.
+ * vit.hip (head dimension 64, L <= 200 tokens, W = 64 * heads): ln_bwd: dx = add (or 0) + the LayerNorm input gradient from
+ *   the kept (mean, rstd).  attn_fwd: qkv [B L][3W] raw + bias [3W] -> A [B L][W], lse [B][heads][L] of the scaled scores.
+ *   attn_bwd: dq, dk, dv into dqkv [B L][3W] (every element written).  slices: the grid's third dimension (query rows or
+ *   keys per workgroup), 0 = what the executor picks from heads and B, else 1 .. 4: the bits do not depend on it.
+ *   drop_cls: dE [B][L-1][W] = dT [B][1 + l].  gram_bwd: dT [L][W] row 0 = 0, row 1 + l = (2 scale / *nrm) FR[l]
+ *   (0 when *nrm is 0); nrm a device pointer. */
+int hedit_k_split3_geometry(int C, int* Cs, int* Kp);
+int hedit_k_split3(const float* x, int ldx, const float* z, const float* p, const float* q, int pq_img, int op, void* out, int Kp,
+                   int Cs, int C, int geo, int B, int H, int W, int worder, int64_t rows_out, void* stream);
+int hedit_k_pack_split3_w(const float* w, const float* scale, void* out, int O, int I, int k, int dgrad, int Cs, int Kp, int rows_out,
+                          int perm_hw, int perm_c, void* stream);
+size_t hedit_k_precise_conv_ws_bytes(int O, int I, int k, int dgrad, int mode, int geo, int B, int Hin, int Win);
+int hedit_k_precise_conv(const float* x, int op, const float* p, const float* q, int pq_img, const float* z, int geo,
+                         const float* w_oihw, const float* scale, int O, int I, int k, int perm_hw, int perm_c, int dgrad, int mode,
+                         int B, int Hin, int Win, float* out, int* chunk_kt, int* splits, void* ws, size_t ws_bytes, void* stream);
+int hedit_k_bn_affine(const float* g, const float* b, const float* m, const float* v, float eps, float* p, float* q, int C, int rep,
+                      void* stream);
+int hedit_k_bn_fold_bias(const float* bias, const float* g, const float* b, const float* m, const float* v, float eps, float* p,
+                         float* q, int C, void* stream);
+int hedit_k_act(const float* x, const float* p, const float* q, float* y, int64_t total, int C, int op, void* stream);
+int hedit_k_se_nslab(int HW);
+int hedit_k_se_pool(const float* u, float* part, int B, int HW, int C, void* stream);
+int hedit_k_se_fc(const float* part, const float* bias, const float* w1, const float* w2, float* hbuf, float* sbuf, int B, int HW,
+                  int C, int R, void* stream);
+int hedit_k_se_combine(const float* u, const float* bias, const float* s, const float* sc, const float* sc_bias, const float* X,
+                       int stride, float* Y, int B, int Ho, int Wo, int C, void* stream);
+int hedit_k_se_bwd_reduce(const float* dY, const float* u, const float* bias, float* part, int B, int HW, int C, void* stream);
+int hedit_k_se_fc_bwd(const float* part, const float* sbuf, const float* hbuf, const float* w1, const float* w2, float* rbuf, int B,
+                      int C, int R, int HW, void* stream);
+int hedit_k_unit_bwd_combine(const float* dxa, const float* p, const float* dsc, int stride, float* dX, int B, int H, int W, int C,
+                             void* stream);
+int hedit_k_scale_cols(const float* x, const float* p, float* y, int64_t total, int n, void* stream);
+int hedit_k_face_pool(const float* img, float* out, int B, void* stream);
+int hedit_k_face_pool_bwd(const float* g, int ldg, float* dimg, int B, void* stream);
+int hedit_k_cos_head(const float* raw, const float* bias, const float* ref, int ref_stride, float* feat, float* loss, float* df,
+                     int B, int D, float scale, void* stream);
+int hedit_k_lpips_prep(const float* img, float* out, const float* shift3, const float* scale3, int B, int H, int W, void* stream);
+int hedit_k_lpips_prep_bwd(const float* g, int ldg, float* dimg, const float* scale3, int B, int H, int W, void* stream);
+int hedit_k_maxpool2(const float* z, float* zp, uint8_t* idx, int B, int H, int W, int C, void* stream);
+int hedit_k_maxpool2_bwd(const float* gp, const uint8_t* idx, const float* add, float* G, int B, int H, int W, int C, void* stream);
+int hedit_k_lpips_head(const float* z, const float* bias, const float* src, int64_t src_img_stride, const float* w, float* fn_out,
+                       float* dpix, float* dF, int B, int HW, int C, float gscale, void* stream);
+int hedit_k_lpips_reduce(const float* dpix, float* acc, int B, int HW, int first, void* stream);
+int hedit_k_enc_patchify(const float* img, float* X, int B, int R, int p, int bwd, void* stream);
+int hedit_k_enc_tokens(const float* E, const float* cbias, const float* cls, const float* pos, float* T, int B, int L, int W,
+                       void* stream);
+int hedit_k_enc_gather_rows(const float* T, const int32_t* idx, float* R, int B, int L, int W, void* stream);
+int hedit_k_enc_ln(const float* x, const float* g, const float* b, float* y, float* stats, int64_t rows, int W, float eps,
+                   void* stream);
+int hedit_k_enc_add_bias_res(const float* raw, const float* bias, const float* res, float* out, int64_t total, int W, void* stream);
+int hedit_k_vit_ln_bwd(const float* x, const float* dy, const float* g, const float* stats, const float* add, float* dx, int64_t rows,
+                       int W, void* stream);
+int hedit_k_vit_attn_fwd(const float* qkv, const float* bias, float* A, float* lse, int B, int L, int heads, int slices,
+                         void* stream);
+int hedit_k_vit_attn_bwd(const float* qkv, const float* bias, const float* A, const float* dA, const float* lse, float* dqkv, int B,
+                         int L, int heads, int slices, void* stream);
+int hedit_k_vit_drop_cls(const float* dT, float* dE, int B, int L, int W, void* stream);
+int hedit_k_vit_gram_bwd(const float* FR, const float* nrm, float* dT, int L, int W, float scale, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,7 @@ SUITE = [
     ("test_gpu_errors.py", None, 4, 4),
     ("test_gpu_gemm_paths.py", None, 33, 33),
     ("test_gpu_grad_kernels.py", None, 80, 80),
+    ("test_gpu_precise_kernels.py", None, 106, 106),
 ]
 
 
