@@ -19,11 +19,15 @@ on the native SqueezeNet-LPIPS (hedit/lpips_score.py, csrc/sqlpips.hip) when LOC
 ``structure_distance`` / ``structure_distance_unedit_part`` / ``structure_distance_edit_part`` (the mean squared difference
 of the DINO ViT-B/8 key self-similarity matrices, matrics_calculator.py:12-246,390-410) run on the native DINO key
 extractor (hedit/dino_score.py, csrc/dino.hip) when a LOCAL state dict is given with ``--dino_path`` (the published
-``dino_vitbase8_pretrain.pth``, or a directory holding exactly one ``.pth``) and ``--device cuda``.  The remaining network
-metric needs third-party checkpoints that do not exist offline and is not part of the sampling path (SURVEY.md section 8
-row f4 "then the evaluator"): ``local_clip`` (prompt templates + CLIP RN50 / ViT-B/32) -- asking for it, or for a CLIP
-score / LPIPS / structure distance without its model, raises with the name of the missing checkpoint instead of writing a
-made-up number.
+``dino_vitbase8_pretrain.pth``, or a directory holding exactly one ``.pth``) and ``--device cuda``.  ``local_clip`` (the CLIP
+directional similarity of local_clip_evaluation.py as matrics_calculator.py:304-307,320-321 runs it: ViT-L/14, the direction
+term alone, masks ignored) runs on the same towers plus the native image preprocessing and direction head
+(hedit/local_clip_score.py, csrc/imgprep.hip) when ``--clip_path`` and ``--local_clip_templates FILE`` are given: the prompt
+templates are the user's input, one per line with one ``{}`` each -- none is shipped.  Asking for a network metric without
+its model raises with the name of what is missing instead of writing a made-up number.
+
+``--native_preprocess`` (with ``--clip_path`` and ``--device cuda``) moves the image preprocessing of the clip_similarity_*
+columns to the device (hedit/image_prep.py): PIL's bicubic resample bit for bit, so the CSV does not change by a byte.
 
 ``--native_pixel`` (with ``--device cuda``) moves the pixel columns themselves to the native executor (hedit/pixel_score.py,
 csrc/pixmetrics.hip): the same formulas on the uint8 images, fp64 after the fp32 difference, binary masks only.  ``--batch N``
@@ -44,7 +48,7 @@ PIXEL_METRICS = ("psnr", "mse", "ssim")
 PIXEL_METRICS_ORDER = ("mse", "psnr", "ssim")        # the columns of a pixel scorer's 3 x 3 result (hedit.pixel_score.METRICS)
 NETWORK_METRICS = {"lpips": "torchmetrics LPIPS (SqueezeNet) weights", "structure_distance": "DINO ViT-B/8 weights (a local state dict: --dino_path)",
                    "clip_similarity_source_image": "CLIP ViT-L/14 weights", "clip_similarity_target_image": "CLIP ViT-L/14 weights",
-                   "clip_similarity_target_image_edit_part": "CLIP ViT-L/14 weights", "local_clip": "CLIP ViT-B/32 weights"}
+                   "clip_similarity_target_image_edit_part": "CLIP ViT-L/14 weights", "local_clip": "a local CLIP ViT-L/14 model (--clip_path) and a prompt-template file (--local_clip_templates)"}
 
 
 def mask_decode(encoded_mask, image_shape=(512, 512)):
@@ -91,9 +95,10 @@ class MetricsCalculator:
     names.  `clip`: a CLIP scorer (hedit.clip_score.NativeClip); without one ``calculate_clip_similarity`` raises.  `lpips`:
     an LPIPS scorer (hedit.lpips_score.NativeSqueezeLpips); without one ``calculate_lpips`` raises.  `dino`: a structure
     scorer (hedit.dino_score.NativeDinoStructure); without one ``calculate_structure_distance`` raises.  `pixel`: a pixel
-    scorer (hedit.pixel_score.NativePixelMetrics); without one ``calculate_mse`` / ``_psnr`` / ``_ssim`` are the torch code below."""
+    scorer (hedit.pixel_score.NativePixelMetrics); without one ``calculate_mse`` / ``_psnr`` / ``_ssim`` are the torch code below.
+    `local_clip`: a directional-similarity scorer (hedit.local_clip_score.NativeLocalClip); without one ``compute_local_clip`` raises."""
 
-    def __init__(self, device="cpu", clip=None, lpips=None, dino=None, pixel=None):
+    def __init__(self, device="cpu", clip=None, lpips=None, dino=None, pixel=None, local_clip=None):
         self.device = device
         self.clip = clip              # hedit.clip_score.NativeClip (or anything with score(uint8 H x W x 3 array, text)), or None
         self.lpips = lpips            # hedit.lpips_score.NativeSqueezeLpips (or anything with score(pred, gt, mask_pred, mask_gt)), or None
@@ -107,6 +112,16 @@ class MetricsCalculator:
         self.pixel = pixel            # hedit.pixel_score.NativePixelMetrics (or anything with score(metric, pred, gt, mask_pred, mask_gt)), or None
         if pixel is not None:
             _require_cuda(device, "native pixel metrics", "the pixel-metrics kernel runs")
+        self.local_clip = local_clip  # hedit.local_clip_score.NativeLocalClip (or anything with score(src, src prompt, tgt, tgt prompt)), or None
+        if local_clip is not None:
+            _require_cuda(device, "local_clip")
+
+    def compute_local_clip(self, src_img, src_prompt, tar_img, tar_prompt, mask=None):
+        """matrics_calculator.py:304-327: the directional similarity of the two images and the two prompts; the reference
+        takes a mask and never uses it (its CLIPLoss runs the direction term alone), so it is ignored here too"""
+        if self.local_clip is None:
+            raise NotImplementedError("local_clip: needs " + NETWORK_METRICS["local_clip"] + ", which this run does not have")
+        return float(self.local_clip.score(src_img, src_prompt, tar_img, tar_prompt))
 
     def calculate_structure_distance(self, img_pred, img_gt, mask_pred=None, mask_gt=None):
         """matrics_calculator.py:390-410: both images as float32 in 0...255 (NOT / 255), times their masks, through the DINO
@@ -180,6 +195,8 @@ def calculate_metric(mc, metric, src_image, tgt_image, src_mask, tgt_mask, src_p
         if tgt_mask.sum() == 0:
             return "nan"
         return mc.calculate_clip_similarity(tgt_image, tgt_prompt, tgt_mask)
+    if metric == "local_clip" and getattr(mc, "local_clip", None) is not None:
+        return mc.compute_local_clip(src_image, src_prompt, tgt_image, tgt_prompt)
     routed = PIXEL_METRICS + (("lpips",) if getattr(mc, "lpips", None) is not None else ()) + \
         (("structure_distance",) if getattr(mc, "dino", None) is not None else ())
     if (base in NETWORK_METRICS or metric in NETWORK_METRICS) and base not in routed:
@@ -220,6 +237,8 @@ def _grouped_request(mc, metric, it):
         if mask.sum() == 0:
             return "nan"
         return "clip", (np.uint8(np.array(tgt) * np.array(mask)), it["tgt_p"])
+    if metric == "local_clip" and getattr(mc, "local_clip", None) is not None:
+        return "local_clip", (src, it["src_p"], tgt, it["tgt_p"])
     base, part = _split_metric(metric)
     family = {"lpips": "lpips", "structure_distance": "dino"}.get(base, "pixel" if base in PIXEL_METRICS else None)
     if family is None or getattr(mc, family, None) is None:
@@ -269,7 +288,7 @@ def evaluate_group(mc, metrics, items):
             continue
         family = calls[0][1][0]
         scorer = getattr(mc, family)
-        if family != "clip":
+        if family not in ("clip", "local_clip"):
             for _, (_, a) in calls:
                 assert np.array(a[0]).shape == np.array(a[1]).shape, "Image shapes should be the same."
         if hasattr(scorer, "scores"):
@@ -305,6 +324,12 @@ def build_parser():
                         "directory holding exactly one .pth")
     p.add_argument('--dino_resolution', type=int, default=224,
                    help="the side the DINO input is resized to; the checkpoint's pos_embed must fit it (no interpolation)")
+    p.add_argument('--local_clip_templates', type=str, default=None,
+                   help="prompt templates of the local_clip metric (needs --clip_path): a UTF-8 file, one template per line with one "
+                        "'{}' each; blank lines and lines starting with # are skipped")
+    p.add_argument('--native_preprocess', action="store_true",
+                   help="preprocess the images of the clip_similarity_* columns on the device (needs --device cuda and --clip_path); "
+                        "the CSV is byte for byte the same")
     p.add_argument('--native_pixel', action="store_true",
                    help="compute the psnr* / mse* / ssim* columns with the native pixel-metrics kernel (needs --device cuda; binary masks)")
     p.add_argument('--batch', type=int, default=1,
@@ -344,6 +369,12 @@ def load_pixel(device):
     _require_cuda(device, "--native_pixel", "the pixel-metrics kernel runs")
     from hedit.pixel_score import NativePixelMetrics
     return NativePixelMetrics(device="cuda:0" if str(device) == "cuda" else device)
+
+
+def load_local_clip(clip, templates_path):
+    """The native local_clip scorer on the towers of --clip_path with the templates of --local_clip_templates"""
+    from hedit.local_clip_score import NativeLocalClip, load_templates
+    return NativeLocalClip(clip, load_templates(templates_path))
 
 
 def _entries(args, folders, annotation):
@@ -397,24 +428,35 @@ def _run_grouped(args, mc, folders, entries):
     return written
 
 
-def main(argv=None, clip=None, lpips=None, dino=None, pixel=None):
-    """`clip` / `lpips` / `dino` / `pixel`: ready scorers instead of --clip_path / --lpips_path / --dino_path / --native_pixel
-    (synthetic runs and tests: NativeClip.from_standin, NativeSqueezeLpips(), NativeDinoStructure(), NativePixelMetrics())"""
+def main(argv=None, clip=None, lpips=None, dino=None, pixel=None, local_clip=None):
+    """`clip` / `lpips` / `dino` / `pixel` / `local_clip`: ready scorers instead of --clip_path / --lpips_path / --dino_path /
+    --native_pixel / --local_clip_templates (synthetic runs and tests: NativeClip.from_standin, NativeSqueezeLpips(),
+    NativeDinoStructure(), NativePixelMetrics(), NativeLocalClip(clip, templates))"""
     args = build_parser().parse_args(argv)
     if args.batch < 1:
         raise SystemExit("--batch N: N >= 1")
     if not args.tgt_folders or len(args.tgt_folders) != len(args.tgt_methods):
         raise SystemExit("give --tgt_folders DIR ... (one per method)")
     folders = dict(zip(args.tgt_methods, args.tgt_folders))
+    if args.local_clip_templates and local_clip is None and clip is None and not args.clip_path:
+        raise SystemExit("--local_clip_templates FILE needs the CLIP towers: give --clip_path too")
+    if args.native_preprocess:
+        _require_cuda(args.device, "--native_preprocess", "the image-preprocessing kernel runs")
+        if clip is None and not args.clip_path:
+            raise SystemExit("--native_preprocess preprocesses the images of the CLIP columns: give --clip_path too")
     if clip is None and args.clip_path:
         clip = load_clip(args.clip_path, args.clip_tokenizer, args.device)
+    if args.native_preprocess:
+        clip.native_preprocess = True
+    if local_clip is None and args.local_clip_templates:
+        local_clip = load_local_clip(clip, args.local_clip_templates)
     if lpips is None and args.lpips_path:
         lpips = load_lpips(args.lpips_path, args.device)
     if dino is None and args.dino_path:
         dino = load_dino(args.dino_path, args.device, args.dino_resolution)
     if pixel is None and args.native_pixel:
         pixel = load_pixel(args.device)
-    mc = MetricsCalculator(args.device, clip, lpips, dino, pixel=pixel)
+    mc = MetricsCalculator(args.device, clip, lpips, dino, pixel=pixel, local_clip=local_clip)
     os.makedirs(os.path.dirname(os.path.abspath(args.result_path)), exist_ok=True)
     with open(args.result_path, 'w', newline="") as f:
         csv.writer(f).writerow(["file_id"] + [f"{k}|{m}" for k in folders for m in args.metrics])
@@ -450,5 +492,5 @@ def main(argv=None, clip=None, lpips=None, dino=None, pixel=None):
 
 if __name__ == "__main__":
     import sys
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # the `hedit` package, for --clip_path / --lpips_path / --dino_path
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))      # the `hedit` package, for the native scorers
     main()

@@ -188,6 +188,10 @@ _SIGS = {    "hedit_last_error": (C.c_char_p, []),
     "hedit_pixel_metrics_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
     "hedit_pixel_metrics": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                       C.c_size_t, C.c_void_p]),
+    "hedit_image_prep_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "hedit_image_prep": (C.c_int, [C.c_void_p] + [C.c_int] * 9 + [C.c_void_p, C.c_void_p, C.c_int] * 2 + [C.c_int, C.c_int] +
+                         [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    "hedit_clip_direction": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     **_family("vae", VaeCfg, False, [C.c_int] * 4),
     "hedit_vae_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                    C.c_size_t, C.c_void_p]),

@@ -276,6 +276,8 @@ class NativeClip:
         if text.proj_dim != image.embed_dim:
             raise ValueError(f"text_projection has {text.proj_dim} columns, visual.proj {image.embed_dim}: not one embedding space")
         self.image, self.text, self.tokenizer = image, text, tokenizer
+        self.native_preprocess = False        # pixel_values on the device (hedit.image_prep) instead of preprocess_pil
+        self._prep = None
 
     # ------------------------------------------------------------------ loaders (local files only)
     @classmethod
@@ -367,12 +369,30 @@ class NativeClip:
                              f"tokenizer's eos_token_id ({eos})")
         return self.text(ids)[1]
 
-    def pixel_values(self, images):
+    def pixel_values(self, images, native=None):
         """(B, 3, R, R) fp32: every PIL image / uint8 (H, W, 3) array through ``preprocess_pil``; a float (3, R, R) tensor is
-        taken as already preprocessed"""
+        taken as already preprocessed.  ``native`` (default: ``self.native_preprocess``, False): the same values computed on
+        the image tower's device by ``hedit.image_prep`` (its transformers convention: bit for bit ``preprocess_pil``'s), one
+        upload and one native call per image size; the tensor then lives on that device."""
         R = self.image.input_resolution
-        return torch.stack([im.detach().float().cpu() if torch.is_tensor(im) and im.is_floating_point() else torch.from_numpy(preprocess_pil(im, R))
-                            for im in images])
+        if not (self.native_preprocess if native is None else native):
+            return torch.stack([im.detach().float().cpu() if torch.is_tensor(im) and im.is_floating_point() else
+                                torch.from_numpy(preprocess_pil(im, R)) for im in images])
+        from .image_prep import NativeImagePrep, image_u8
+        dev = self.image.device
+        if self._prep is None or self._prep.device != dev:
+            self._prep = NativeImagePrep(dev)
+        out, by_size = [None] * len(images), {}
+        for i, im in enumerate(images):
+            if torch.is_tensor(im) and im.is_floating_point():
+                out[i] = im.detach().float().to(dev)
+            else:
+                a = image_u8(im)
+                by_size.setdefault(a.shape, []).append((i, a))
+        for group in by_size.values():
+            for (i, _), x in zip(group, self._prep([a for _, a in group], R, "transformers")):
+                out[i] = x
+        return torch.stack(out)
 
     def image_features(self, images):
         """(B, embed_dim) fp32, not normalised; ONE native call for the whole list of PIL images / uint8 (H, W, 3) arrays /

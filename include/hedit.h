@@ -880,6 +880,45 @@ size_t hedit_pixel_metrics_workspace_bytes(int N, int height, int width);
 int hedit_pixel_metrics(const uint8_t* pred, const uint8_t* gt, const uint8_t* mask_pred, const uint8_t* mask_gt, int N, int height,
                         int width, double* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Image preprocessing of the evaluator's CLIP metrics (csrc/imgprep.hip): PIL's Image.resize on 8-bit RGB, a crop and a
+ * per-channel look-up, bit for bit.  src: uint8 [B][H][W][3] (what np.array(PIL image) holds).  The image is resampled to
+ * resized_height x resized_width by Pillow's two passes (horizontal, then vertical, the intermediate rounded and clamped to
+ * uint8; 22-bit fixed-point taps, int32 accumulator starting at 1 << 21, clamp(acc >> 22, 0, 255)), of which only the window
+ * [top, top + crop_height) x [left, left + crop_width) is computed.  out: fp32 [B][3][crop_height][crop_width] =
+ * lut[channel][pixel], lut fp32 [3][256]; out_u8 (may be null): the pixels themselves, uint8 [B][crop_height][crop_width][3].
+ * The filter is the caller's: taps_x int32 [resized_width][ksize_x] and bounds_x int32 [resized_width][2] = (first source
+ * index, count <= ksize_x) per output column, taps_y / bounds_y / ksize_y likewise per output row, all in device memory
+ * (hedit/image_prep.py builds Pillow's bilinear and bicubic tables).  A null taps / bounds pair means that axis keeps its size
+ * (Pillow skips the pass).  row0, nrows: the source rows the crop's vertical taps read, [min first, max first + count) over
+ * the crop's rows (top, crop_height when the height is unchanged); a pair of the table that leaves that range is cut to it.
+ * Two launches through a uint8 workspace [B][nrows][crop_width][3], no atomics, nothing synchronises; image b has the bits of
+ * the B = 1 call, in either storage build.  HEDIT_ERR_ARG, before anything is launched, for a null src / lut / out /
+ * workspace, B outside [1, HEDIT_IMAGE_PREP_MAX_BATCH], H, W or a resized size outside [1, 16384], a crop that leaves the
+ * resized image, a null table for an axis whose size changes, ksize outside [1, HEDIT_IMAGE_PREP_MAX_TAPS], source rows that
+ * leave the image, or a workspace below hedit_image_prep_workspace_bytes(B, nrows, crop_width) (0 for arguments out of range). */
+#define HEDIT_IMAGE_PREP_MAX_BATCH 64
+#define HEDIT_IMAGE_PREP_MAX_TAPS 1024
+size_t hedit_image_prep_workspace_bytes(int B, int nrows, int crop_width);
+int hedit_image_prep(const uint8_t* src, int B, int height, int width, int resized_height, int resized_width, int top, int left,
+                     int crop_height, int crop_width, const int32_t* taps_x, const int32_t* bounds_x, int ksize_x,
+                     const int32_t* taps_y, const int32_t* bounds_y, int ksize_y, int row0, int nrows, const float* lut, float* out,
+                     uint8_t* out_u8, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The head of the evaluator's local_clip column (clip_directional_loss with the DirectionMetric of
+ * text-guided/evaluation/local_clip_evaluation.py), P pairs in one launch, one workgroup per pair.
+ * txt: fp32 [P][2][T][E], the T template prompts of the source prompt (index 0) and of the target prompt (index 1) as the text
+ * tower returns them; img: fp32 [P][2][E], source image then target image; out: double [P].  In fp64 after the loads:
+ * s^_j = s_j / |s_j|, t^_j = t_j / |t_j|; d = sum_j (t^_j - s^_j) / T with j in index order; D = d / |d|; a^ = a / |a|,
+ * b^ = b / |b|; e = b^ - a^; e^ = e / (|e| + 1e-7); out = e^ . D / (max(|e^|, 1e-8) max(|D|, 1e-8)).  Every reduction over E
+ * is a fixed tree that depends on E alone: out[p] has the bits of the P = 1 call, in either storage build.  Equal image
+ * features give exactly 0.0, equal prompt features NaN (the reference's 0 / 0).  HEDIT_ERR_ARG, before the launch, for a null
+ * pointer, P outside [1, 64], T outside [1, 256], E not a multiple of 4 or above 4096, or an out that is not 8-byte aligned. */
+#define HEDIT_CLIP_DIRECTION_MAX_PAIRS 64
+#define HEDIT_CLIP_DIRECTION_MAX_TEMPLATES 256
+#define HEDIT_CLIP_DIRECTION_MAX_DIM 4096
+int hedit_clip_direction(const float* txt, const float* img, int P, int T, int E, double* out, void* stream);
+
 /* ---- single kernels (parity tests), precise family ------------------------------------------------
  * The kernels of the "precise" path (csrc/pnet.hip, encoder.hip, the attention / LayerNorm gradient kernels of vit.hip) one
  * by one, for tests/test_gpu_precise_kernels.py.  Thin wrappers: no product kernel and no dispatch is changed by them.  All
