@@ -148,6 +148,13 @@ int hedit_local_blend_sub(float* const* h_maps, int n_maps, int heads, const flo
                             H, W, th, th_sub, S(stream));
 } catch (...) { return hedit_abi_catch(); }
 
+int hedit_attn_aggregate(float* const* h_maps, int n_maps, int heads, int tokens, int cols, int n_img, int cur_step, float* out,
+                         void* stream) try {
+  ARG_CHECK(h_maps, "attn_aggregate: h_maps is null");
+  ARG_CHECK(out, "attn_aggregate: out is null");
+  return attn_aggregate_launch(const_cast<const float* const*>(h_maps), n_maps, heads, tokens, cols, n_img, cur_step, out, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
 int hedit_axis_mix(const float* in, float* out, const int32_t* idx, const float* val, int nnz, int64_t outer, int n_in, int n_out, int inner,
                    void* stream) try {
   ARG_CHECK(in && out && idx && val, "axis_mix args");

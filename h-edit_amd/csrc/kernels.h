@@ -321,6 +321,11 @@ int axis_mix_launch(const float* in, float* out, const int* idx, const float* va
                     hipStream_t st);
 int local_blend_launch(const float* const* maps, int n_maps, int heads, const float* alpha_layers, const float* alpha_sub,
                        const int* enabled, float* xt, int n_img, int C, int H, int W, float th, float th_sub, hipStream_t st);
+// aggregate_attention: maps[l] [n_img][2][heads][tokens][cols] accumulators -> out [n_img][2][tokens][cols], the mean over
+// maps and heads of acc / cur_step, summed map-major then head-ascending in fp32 (maps: HOST array of device pointers)
+#define HEDIT_AGG_MAX_MAPS 16
+int attn_aggregate_launch(const float* const* maps, int n_maps, int heads, int tokens, int cols, int n_img, int cur_step,
+                          float* out, hipStream_t st);
 
 // ---------------------------------------------------------------- pnet.hip ("precise" fp32-quality building blocks)
 // ops of the fused element-wise stage that produces a split-bf16 GEMM operand (and of act_launch)

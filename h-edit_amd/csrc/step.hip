@@ -233,6 +233,55 @@ __global__ __launch_bounds__(256) void local_blend_kernel(BlendMaps maps, int n_
   }
 }
 
+struct AggMaps { const float* p[HEDIT_AGG_MAX_MAPS]; };
+
+// aggregate_attention (p2p/ptp_classes.py:298-309) over the accumulated maps of a lock-step batch, both prompts of every
+// pair in one launch: maps[l] is [n_img][2][heads][E], E = tokens * cols, out is [n_img][2][E] and per element
+//   out = ((m_0,0 / s + m_0,1 / s) + ... + m_L-1,H-1 / s) / (L * H),   s = cur_step,
+// map-major then head-ascending, every operation a rounded fp32 one (this unit is built with -ffp-contract=off).  One
+// thread owns V consecutive elements of the FLAT [tokens * cols] slab and walks the L * H slabs above them: the order
+// depends on nothing but (L, H), so image i of a batch has the bits of a single-image call, and no row of 77 columns
+// is ever addressed on its own.  V = 4: 128-bit accesses (E % 4 == 0 and 16-byte aligned bases, checked by the
+// launcher); V = 1 otherwise.  A pure streaming read: no LDS, no atomics, the grid covers E exactly once.
+template <int V>
+__global__ __launch_bounds__(256) void attn_aggregate_kernel(AggMaps maps, int n_maps, int heads, long E, float steps,
+                                                             float count, float* __restrict__ out) {
+  const long e = ((long)blockIdx.x * blockDim.x + threadIdx.x) * V;
+  if (e >= E) return;
+  const long slab = blockIdx.y;                      // img * 2 + prompt
+  alignas(16) float acc[V];
+#pragma unroll
+  for (int v = 0; v < V; ++v) acc[v] = 0.f;
+  constexpr int HB = 8;                              // head slabs loaded before the first is consumed (SD: all 8 heads of a map)
+  for (int l = 0; l < n_maps; ++l) {
+    const float* src = maps.p[l] + slab * heads * E + e;
+    int h = 0;
+    for (; h + HB <= heads; h += HB) {
+      alignas(16) float m[HB][V];
+#pragma unroll
+      for (int j = 0; j < HB; ++j) {
+        if (V == 4) *reinterpret_cast<float4*>(m[j]) = *reinterpret_cast<const float4*>(src + (long)(h + j) * E);
+        else m[j][0] = src[(long)(h + j) * E];
+      }
+#pragma unroll
+      for (int j = 0; j < HB; ++j)
+#pragma unroll
+        for (int v = 0; v < V; ++v) acc[v] = acc[v] + m[j][v] / steps;
+    }
+    for (; h < heads; ++h) {
+      alignas(16) float m[V];
+      if (V == 4) *reinterpret_cast<float4*>(m) = *reinterpret_cast<const float4*>(src + (long)h * E);
+      else m[0] = src[(long)h * E];
+#pragma unroll
+      for (int v = 0; v < V; ++v) acc[v] = acc[v] + m[v] / steps;
+    }
+  }
+#pragma unroll
+  for (int v = 0; v < V; ++v) acc[v] = acc[v] / count;
+  if (V == 4) *reinterpret_cast<float4*>(out + slab * E + e) = *reinterpret_cast<const float4*>(acc);
+  else out[slab * E + e] = acc[0];
+}
+
 // ---- style guidance (text-guided-n-style/inversion/h_edit.py:160-185) around the decoder / image-encoder pass
 // z0 = (x - sqrt(1-ab) e_tar) / sqrt(ab) * inv_scale : Tweedie x0 at t-1, pre-divided by the VAE scaling factor
 __global__ __launch_bounds__(256) void step_tweedie_kernel(const float* __restrict__ e_u_tar, const float* __restrict__ e_c_tar,
@@ -427,6 +476,39 @@ int local_blend_launch(const float* const* maps, int n_maps, int heads, const fl
   for (int i = 0; i < 8; ++i) bm.p[i] = i < n_maps ? maps[i] : nullptr;
   hipLaunchKernelGGL(local_blend_kernel, dim3(n_img), dim3(256), 0, st, bm, n_maps, heads, alpha_layers, alpha_sub, enabled, xt, n_img, C, H,
                      W, th, th_sub);
+  LAUNCH_CHECK();
+  return HEDIT_OK;
+}
+
+int attn_aggregate_launch(const float* const* maps, int n_maps, int heads, int tokens, int cols, int n_img, int cur_step,
+                          float* out, hipStream_t st) {
+  ARG_CHECK(n_maps >= 1, "attn_aggregate: n_maps < 1 (no map selected)");
+  ARG_CHECK(n_maps <= HEDIT_AGG_MAX_MAPS, "attn_aggregate: more than 16 maps in one call");
+  ARG_CHECK(cur_step >= 1, "attn_aggregate: cur_step < 1 (nothing accumulated yet)");
+  ARG_CHECK(heads >= 1, "attn_aggregate: heads < 1");
+  ARG_CHECK(cols >= 1, "attn_aggregate: cols < 1");
+  ARG_CHECK(tokens >= 1, "attn_aggregate: tokens < 1");
+  ARG_CHECK(n_img >= 1 && n_img <= 32767, "attn_aggregate: n_img must be 1..32767");
+  ARG_CHECK((long)n_maps * heads < (1 << 24), "attn_aggregate: n_maps * heads is not exact in fp32");
+  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+  const long E = (long)tokens * cols;
+  AggMaps am;
+  bool vec = E % 4 == 0 && al16(out);
+  for (int i = 0; i < HEDIT_AGG_MAX_MAPS; ++i) {
+    am.p[i] = i < n_maps ? maps[i] : nullptr;
+    ARG_CHECK(i >= n_maps || am.p[i], "attn_aggregate: null map pointer");
+    vec = vec && al16(am.p[i]);
+  }
+  const long per = vec ? E / 4 : E;
+  // few elements (the 16 x 16 cross maps: 4928 vectors per slab): one wave per block, so that the slabs still spread
+  // over the CUs; the summation order of an element does not depend on the block size
+  const int block = cdiv(per, 256) * 2L * n_img >= 1024 ? 256 : 64;
+  const long gx = (per + block - 1) / block;
+  ARG_CHECK(gx <= 0x7fffffffL, "attn_aggregate: tokens * cols too large for one launch");
+  dim3 grid((unsigned)gx, 2 * n_img);
+  const float steps = (float)cur_step, count = (float)(n_maps * heads);
+  if (vec) hipLaunchKernelGGL(attn_aggregate_kernel<4>, grid, dim3(block), 0, st, am, n_maps, heads, E, steps, count, out);
+  else hipLaunchKernelGGL(attn_aggregate_kernel<1>, grid, dim3(block), 0, st, am, n_maps, heads, E, steps, count, out);
   LAUNCH_CHECK();
   return HEDIT_OK;
 }

@@ -140,6 +140,7 @@ _SIGS = {    "hedit_last_error": (C.c_char_p, []),
                                     C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "hedit_local_blend_sub": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p]),
+    "hedit_attn_aggregate": (C.c_int, [C.POINTER(C.c_void_p)] + [C.c_int] * 6 + [C.c_void_p, C.c_void_p]),
     **_family("ddpm", DdpmCfg, False, [C.c_int]),
     "hedit_ddpm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p, C.c_void_p, C.c_size_t,
                                      C.c_void_p]),

@@ -16,6 +16,10 @@ reads the source row's Q and K".  The attention store keeps the cross maps only 
 also keeps <=32x32 self maps but nothing on the h-Edit path reads them) and is accumulated
 in-kernel on save_attn passes.
 
+The attention viewers of the same file (aggregate_attention :298-309, show_cross_attention :312-325,
+show_self_attention_comp :328-341, run_and_display :343-348) read those accumulators: one hedit_attn_aggregate launch
+reduces them over heads and layers for the whole batch.
+
 A controller edits ONE (source, target) prompt pair, exactly like the reference;
 ``ControllerBatch`` stacks several for image-batched sampling (build-side generalisation,
 SURVEY.md section 0.1).
@@ -484,6 +488,119 @@ def get_equalizer(text, word_select, values, tokenizer):
         inds = ptp_utils.get_word_inds(text, word, tokenizer)
         equalizer[:, inds] = values
     return equalizer
+
+
+# ---------------------------------------------------------------------------------------------- attention viewers
+def _fused_state(attention_store):
+    """the _PlanState whose buffers the store's lists are views of (the fused path), or None (a Python controller on the
+    hook path, whose store holds plain tensors)"""
+    state = getattr(attention_store, "_state", None)
+    if state is not None and attention_store.attention_store is state.attention_store:
+        return state
+    return None
+
+
+def _no_layer(res, kind, from_where, present):
+    return ValueError(f"aggregate_attention: no {kind}-attention layer of {res} x {res} tokens in {tuple(from_where)}; "
+                      f"resolutions present there: {sorted(present)}")
+
+
+def aggregate_attention(attention_store, res, from_where, is_cross, select, prompts=None, image=None):
+    """The mean over heads and over the layers of ``from_where`` with res x res tokens of the step-averaged attention maps
+    of prompt ``select`` (reference ptp_classes.py:298-309) -> CPU tensor (res, res, 77) for cross maps, (res, res, res^2)
+    for self maps.  Fused path (the store's lists are views of the buffers the attention kernels accumulate into): the
+    buffers are selected by place and token count and reduced for every image and both prompts by ONE hedit_attn_aggregate
+    launch -- acc / cur_step summed map-major then head-ascending in fp32, divided by the count -- and ``select`` is a
+    slice of its result.  Hook path (a Python controller's store of plain tensors): the reference's torch composition.
+    ``image`` (addition): the pair of a ControllerBatch.  Self maps are kept on request only (store_self_maps)."""
+    kind = "cross" if is_cross else "self"
+    tokens = res * res
+    state = _fused_state(attention_store)
+    if state is None:
+        maps = attention_store.get_average_attention()
+        n_prompts = 2 if prompts is None else len(prompts)
+        present, picked = set(), []
+        for location in from_where:
+            for item in maps.get(f"{location}_{kind}", []):
+                present.add(int(round(item.shape[1] ** 0.5)))
+                if item.shape[1] == tokens:
+                    picked.append(item.reshape(n_prompts, -1, res, res, item.shape[-1])[select])
+        if not picked:
+            raise _no_layer(res, kind, from_where, present)
+        out = torch.cat(picked, dim=0)
+        return (out.sum(0) / out.shape[0]).cpu()
+    if select not in (0, 1):
+        raise ValueError("select: 0 (source prompt) or 1 (target prompt)")
+    if image is None:
+        if state.n != 1:
+            raise ValueError(f"a batch of {state.n} pairs: say which with image=")
+        image = 0
+    if not 0 <= image < state.n:
+        raise ValueError(f"image = {image} outside the batch of {state.n}")
+    bufs = state.bufs if is_cross else state.self_bufs
+    if not bufs:
+        raise RuntimeError("the self-attention maps were not stored: create the controller with store_self_maps=True (or set "
+                           "controller.store_self_maps = True before the first UNet pass)")
+    places = set(from_where)
+    present = {int(round(tok ** 0.5)) for tok, place in state.layers if place in places}
+    picked = [buf for location in from_where for (tok, place), buf in zip(state.layers, bufs) if place == location and tok == tokens]
+    if not picked:
+        raise _no_layer(res, kind, from_where, present)
+    cols = picked[0].shape[-1]
+    heads = picked[0].shape[2]
+    out = torch.empty(state.n, 2, tokens, cols, dtype=torch.float32, device=picked[0].device)
+    arr = (C.c_void_p * len(picked))(*[b.data_ptr() for b in picked])
+    with torch.cuda.device(out.device):
+        _lib.check(_lib.lib().hedit_attn_aggregate(arr, len(picked), heads, tokens, cols, state.n, int(attention_store.cur_step),
+                                                   _lib.ptr(out), _lib.cur_stream()))
+    return out[image, select].reshape(res, res, cols).cpu()
+
+
+def show_cross_attention(attention_store, res, from_where, select=0, prompts=None, tokenizer=None, image=None):
+    """One 256 x 256 tile per token of prompts[select], its aggregated cross map scaled to the map's maximum, the token
+    underneath (reference ptp_classes.py:312-325) -> the PIL grid."""
+    from PIL import Image
+    tokens = tokenizer.encode(prompts[select])
+    attention_maps = aggregate_attention(attention_store, res, from_where, True, select, prompts, image=image)
+    images = []
+    for i in range(len(tokens)):
+        tile = attention_maps[:, :, i]
+        tile = 255 * tile / tile.max()
+        tile = tile.unsqueeze(-1).expand(*tile.shape, 3).numpy().astype(np.uint8)
+        tile = np.array(Image.fromarray(tile).resize((256, 256)))
+        images.append(ptp_utils.text_under_image(tile, tokenizer.decode(int(tokens[i]))))
+    return ptp_utils.view_images(np.stack(images, axis=0))
+
+
+def show_self_attention_comp(attention_store, res, from_where, max_com=10, select=0, prompts=None, image=None):
+    """The first max_com right singular vectors of the row-centred aggregated self map as 256 x 256 tiles in one row
+    (reference ptp_classes.py:328-341; the SVD is numpy's, on the host) -> the PIL grid, which the reference drops."""
+    from PIL import Image
+    maps = aggregate_attention(attention_store, res, from_where, False, select, prompts, image=image)
+    maps = maps.numpy().reshape((res ** 2, res ** 2))
+    _, _, vh = np.linalg.svd(maps - np.mean(maps, axis=1, keepdims=True))
+    images = []
+    for i in range(max_com):
+        tile = vh[i].reshape(res, res)
+        tile = tile - tile.min()
+        tile = 255 * tile / tile.max()
+        tile = np.repeat(np.expand_dims(tile, axis=2), 3, axis=2).astype(np.uint8)
+        images.append(np.array(Image.fromarray(tile).resize((256, 256))))
+    return ptp_utils.view_images(np.concatenate(images, axis=1))
+
+
+def run_and_display(model, prompts, controller, latent=None, run_baseline=False, generator=None):
+    """Generate the pair under ``controller`` (after the same pair under EmptyControl when run_baseline), decode and lay the
+    images out with view_images (the notebook helper of Prompt-to-Prompt; the reference's copy, ptp_classes.py:343-348,
+    breaks off in the middle of its call) -> (uint8 images (2,H,W,3), x_T)."""
+    if run_baseline:
+        print("w.o. prompt-to-prompt")
+        _, latent = run_and_display(model, prompts, EmptyControl(), latent=latent, run_baseline=False, generator=generator)
+        print("with prompt-to-prompt")
+    latents, x_t = ptp_utils.text2image_ldm_stable(model, prompts, controller, latent=latent, generator=generator)
+    images = ptp_utils.latent2image(model.vae, latents)
+    ptp_utils.view_images(images)
+    return images, x_t
 
 
 from ..utils.utils import load_512  # noqa: E402,F401  (reference: p2p/ptp_classes.py:351-373)

@@ -50,3 +50,35 @@ class DDIMScheduler:
         self.timesteps = torch.from_numpy(ts)
         if device is not None:
             self.timesteps = self.timesteps.to(device)
+
+    def step(self, noise_pred, t, latents):
+        """The deterministic (eta = 0) reverse step the Prompt-to-Prompt generation loop takes (p2p/ptp_utils.py:176):
+        x_prev = sqrt(ab_prev) (x - sqrt(1 - ab_t) e) / sqrt(ab_t) + sqrt(1 - ab_prev) e.  The arithmetic is hedit_step_pair's
+        with noise_coef = 0 (csrc/step.hip::ddpm_mu), called with e_u = e_c = noise_pred; there is no second formula here.
+        -> an object that answers both ``["prev_sample"]`` and ``.prev_sample``."""
+        import ctypes as C
+
+        from . import _lib
+        from .engine import Schedule
+        if self.num_inference_steps is None:
+            raise ValueError("DDIMScheduler.step: call set_timesteps first")
+        t = int(t)
+        if t not in self.timesteps.tolist():
+            raise ValueError(f"DDIMScheduler.step: t = {t} is not one of the {self.num_inference_steps} timesteps")
+        for x in (noise_pred, latents):
+            if not (x.is_cuda and x.dtype == torch.float32):
+                raise TypeError("DDIMScheduler.step runs in the HIP step kernel: float32 CUDA tensors expected")
+        if noise_pred.shape != latents.shape:
+            raise ValueError("noise_pred and latents must have one shape")
+        e, x = noise_pred.contiguous(), latents.contiguous()
+        out = torch.empty_like(x)
+        coef = Schedule(self).step_coef(t, 0, 0.0, False, (0.0, 0.0, 0.0), coeff=0.0)
+        _lib.check(_lib.lib().hedit_step_pair(_lib.ptr(e), _lib.ptr(e), _lib.ptr(x), None, _lib.ptr(out), x.shape[0],
+                                              x[0].numel(), 1, C.byref(coef), _lib.cur_stream()))
+        return SchedulerOutput(prev_sample=out)
+
+
+class SchedulerOutput(dict):
+    @property
+    def prev_sample(self):
+        return self["prev_sample"]

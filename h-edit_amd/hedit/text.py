@@ -74,7 +74,9 @@ class WordTokenizer:
         return [self.bos_token_id] + [self._id(w) for w in text.split(" ") if w != ""] + [self.eos_token_id]
 
     def decode(self, ids):
-        sp = {self.bos_token_id: "<|startoftext|>", self.eos_token_id: "<|endoftext|>"}
+        if isinstance(ids, int):          # one id, as CLIPTokenizer.decode accepts it (the attention viewers label maps so)
+            ids = [ids]
+        sp ={self.bos_token_id: "<|startoftext|>", self.eos_token_id: "<|endoftext|>"}
         return "".join(sp.get(int(i), self._words.get(int(i), "?")) for i in ids)
 
     def __call__(self, prompts, padding="max_length", max_length=None, truncation=True, return_tensors="pt"):

@@ -25,6 +25,8 @@
  *                                     text-guided/p2p/ptp_utils.py:98-106 on materialised probabilities (slow path)
  *   hedit_local_blend       replaces  LocalBlend.__call__/get_mask (p2p/ptp_classes.py:44-72)
  *   hedit_local_blend_sub   the same  with substruct_words (p2p/ptp_classes.py:28-38,64-68)
+ *   hedit_attn_aggregate    replaces  aggregate_attention (p2p/ptp_classes.py:298-309): the mean over layers and heads of the
+ *                                     averaged maps the attention viewers display
  *   hedit_p2p_plan          carries   the per-call edit rule of the registered controller / editor: Prompt-to-Prompt
  *                                     (ptp_classes.py:194-227), MasaCtrl (masactrl/masactrl.py:53-69: kv_src) and
  *                                     Plug-and-Play (plug_n_play/pnp_utils.py:29-154: qk_first_block, feat_src)
@@ -308,6 +310,15 @@ int hedit_local_blend(float* const* h_maps, int n_maps, int heads, const float* 
 int hedit_local_blend_sub(float* const* h_maps, int n_maps, int heads, const float* alpha_layers,
                           const float* substruct_layers, const int32_t* enabled, float* xt, int n_img, int C, int H,
                           int W, float th, float th_sub, void* stream);
+/* aggregate_attention (p2p/ptp_classes.py:298-309) for every image of a lock-step batch and both prompts of each pair, in
+ * one launch.  h_maps = HOST array of n_maps (<= 16) device pointers to accumulated maps, each
+ * [n_img][2][heads][tokens][cols] fp32 (cols = 77 for cross maps, tokens for self maps; the caller has selected them by
+ * place and tokens == res * res); out [n_img][2][tokens][cols].  Per element, in fp32:
+ *   out = (t_0,0 + t_0,1 + ... + t_L-1,H-1) / (n_maps * heads),   t_l,h = map_l[.., h, ..] / cur_step (a true division),
+ * summed left to right, map-major then head-ascending: image i of a batch has the bits of a single-image call.
+ * Refused before anything is launched: n_maps < 1 (or > 16), cur_step < 1, heads < 1, cols < 1, tokens < 1, null pointers. */
+int hedit_attn_aggregate(float* const* h_maps, int n_maps, int heads, int tokens, int cols, int n_img, int cur_step,
+                         float* out, void* stream);
 
 /* ---- image autoencoder (SD-1.x AutoencoderKL): the steps either side of the editing loop ---------
  * replaces `model.vae.encode(image).latent_dist.mode()` (text-guided/main_p2p.py:159; also
