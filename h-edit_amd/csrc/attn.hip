@@ -44,24 +44,6 @@ struct HeadCfg {
   static constexpr int DCH = D / 8;               // 16-byte chunks per K row
 };
 
-__device__ __forceinline__ bf16x8 pack_p8(const float* p) {
-  union { uint32_t u[4]; bf16x8 v; } x;
-  x.u[0] = pack_bf16x2(p[0], p[1]);
-  x.u[1] = pack_bf16x2(p[2], p[3]);
-  x.u[2] = pack_bf16x2(p[4], p[5]);
-  x.u[3] = pack_bf16x2(p[6], p[7]);
-  return x.v;
-}
-
-// read the V^T-style A-fragment: row `row`, kv columns {c0..c0+3} and {c0+8..c0+11}
-__device__ __forceinline__ bf16x8 read_perm_frag(const bf16_t* base, int row, int stride, int c0) {
-  union { uint2 h[2]; bf16x8 v; } x;
-  const bf16_t* p = base + row * stride + c0;
-  x.h[0] = *reinterpret_cast<const uint2*>(p);
-  x.h[1] = *reinterpret_cast<const uint2*>(p + 8);
-  return x.v;
-}
-
 // ============================================================================ self-attention
 // Flash attention over 64-row KV tiles, organised around what limits it on CDNA4: per 32x32 score
 // block a lane has ~55 VALU instructions of softmax work (sub, exp2, max, bf16 pack) against

@@ -383,6 +383,29 @@ int hedit_k_self_attn(const void* q, int ldq, const void* k, int ldk, const void
   return self_attn_launch(p, S(stream));
 } catch (...) { return hedit_abi_catch(); }
 
+int hedit_k_masked_self_attn(const void* q, int ldq, const void* k, int ldk, const void* vt, int64_t ldvt, void* out, int ldo,
+                             int B, int N, int heads, int d, const int32_t* rows, int n_rows, const int32_t* kv_src,
+                             const uint8_t* cls_q, const uint8_t* cls_k, void* stream) try {
+  ARG_CHECK(q && k && vt && out && rows && kv_src && cls_q && cls_k, "masked_self_attn args");
+  MaskedSelfAttnParams p{};
+  p.q = reinterpret_cast<const bf16_t*>(q); p.ldq = ldq;
+  p.k = reinterpret_cast<const bf16_t*>(k); p.ldk = ldk;
+  p.vt = reinterpret_cast<const bf16_t*>(vt); p.ldvt = (long)ldvt;
+  p.out = reinterpret_cast<bf16_t*>(out); p.ldo = ldo;
+  p.B = B; p.N = N; p.heads = heads; p.d = d;
+  p.rows = rows; p.n_rows = n_rows; p.kv_src = kv_src; p.cls_q = cls_q; p.cls_k = cls_k;
+  return masked_self_attn_launch(p, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_masa_accumulate(const float* probs, int heads, int rows, const int32_t* ref_tokens, int n_ref,
+                            const int32_t* cur_tokens, int n_cur, float* acc, void* stream) try {
+  return masa_accumulate_launch(probs, heads, rows, ref_tokens, n_ref, cur_tokens, n_cur, acc, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
+int hedit_k_masa_auto_mask(const float* acc, int count, int n, int res, float thres, uint8_t* cls, void* stream) try {
+  return masa_auto_mask_launch(acc, count, n, res, thres, cls, S(stream));
+} catch (...) { return hedit_abi_catch(); }
+
 int hedit_k_cross_attn(const void* q, int ldq, const void* k, int ldk, const void* vt, int64_t ldvt, void* out, int ldo,
                        int B, int N, int heads, int d, const hedit_p2p_plan* plan, float* store, void* stream) try {
   ARG_CHECK(q && k && vt && out && plan, "cross_attn args");

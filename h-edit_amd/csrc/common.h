@@ -207,6 +207,27 @@ __device__ __forceinline__ uint4 pack8(const float* f) {
   return v;
 }
 
+// ---- MFMA fragment helpers shared by the attention kernels (attn.hip, maskattn.hip)
+// eight fp32 probabilities -> one B-operand register pair
+__device__ __forceinline__ bf16x8 pack_p8(const float* p) {
+  union { uint32_t u[4]; bf16x8 v; } x;
+  x.u[0] = pack_bf16x2(p[0], p[1]);
+  x.u[1] = pack_bf16x2(p[2], p[3]);
+  x.u[2] = pack_bf16x2(p[4], p[5]);
+  x.u[3] = pack_bf16x2(p[6], p[7]);
+  return x.v;
+}
+
+// the V^T-style A-fragment: row `row`, kv columns {c0..c0+3} and {c0+8..c0+11} (the kv a lane's 8 packed probabilities of a
+// 32 x 32 score block belong to)
+__device__ __forceinline__ bf16x8 read_perm_frag(const bf16_t* base, int row, int stride, int c0) {
+  union { uint2 h[2]; bf16x8 v; } x;
+  const bf16_t* p = base + row * stride + c0;
+  x.h[0] = *reinterpret_cast<const uint2*>(p);
+  x.h[1] = *reinterpret_cast<const uint2*>(p + 8);
+  return x.v;
+}
+
 static inline int ew_grid(long work_items) {
   long g = (work_items + 255) / 256;
   if (g > 8192) g = 8192;

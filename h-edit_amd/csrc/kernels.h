@@ -259,6 +259,30 @@ int attn_probs_launch(const AttnProbsParams& p, hipStream_t st);
 int attn_self_store_launch(const AttnProbsParams& p, hipStream_t st);
 int attn_apply_launch(const AttnProbsParams& p, hipStream_t st);
 
+// ---------------------------------------------------------------- maskattn.hip
+// Mask-guided mutual self-attention (text-guided/masactrl/masactrl.py:71-148): query i of a listed row attends to the keys
+// of row kv_src[b] whose class equals its own; a query whose class has no key at all attends to every key (the fp32
+// behaviour of the reference's additive finfo.min fill: a uniform softmax over all N keys).  Flash style, one pass.
+struct MaskedSelfAttnParams {
+  const bf16_t* q; int ldq;     // as SelfAttnParams (q pre-scaled by scale*log2(e))
+  const bf16_t* k; int ldk;
+  const bf16_t* vt; long ldvt;
+  bf16_t* out; int ldo;
+  int B, N, heads, d;
+  const int* rows; int n_rows;  // batch rows this launch computes and writes; no other row of `out` is touched
+  const int* kv_src;            // [B] row whose k, v AND key classes row b reads
+  const uint8_t* cls_q;         // [B][N] class (0 / 1) of query i of row b
+  const uint8_t* cls_k;         // [B][N] class of key j of row b (read at row kv_src[b])
+};
+int masked_self_attn_launch(const MaskedSelfAttnParams& p, hipStream_t st);
+// the auto variant's masks (masactrl.py:151-286).  accumulate: acc [rows][256] += head mean of the summed token columns of
+// probs [rows * heads][256][77] (rows < rows / 2 the `ref` tokens, the others `cur`).  auto_mask: acc [2 n][256] (n source
+// maps, n target maps) / count -> per-image min-max normalisation, >= thres, nearest to res x res -> cls [4 n][res * res]
+// (key masks in rows i and 2 n + i, query masks in rows n + i and 3 n + i; a constant map gives class 0)
+int masa_accumulate_launch(const float* probs, int heads, int rows, const int* ref, int n_ref, const int* cur, int n_cur, float* acc,
+                           hipStream_t st);
+int masa_auto_mask_launch(const float* acc, int count, int n, int res, float thres, uint8_t* cls, hipStream_t st);
+
 // ---------------------------------------------------------------- attnbwd.hip
 // Attention backward, flash style (no T x T tensor, no atomics).  Plain attention only (no qk_src / kv_src, no P2P mixing).
 struct AttnBwdParams {

@@ -251,6 +251,8 @@ struct Fwd {
   int rblock = 0;            // ResNet blocks visited so far (PnP feature injection)
   int place = 0;             // 0 down, 1 mid, 2 up: where the transformer block being executed sits (the hook's argument)
   int hook_layer = 0;        // attention layers handed to the hook so far in this call
+  int masa_count = 0;        // plan.masa_auto: 256-token cross-attention layers folded into the accumulator so far in this call
+  int masa_layer = 0;        // plan.masa_auto: self-attention layers under kv_src so far (index into h_masa_dump)
   const RowMap* map = nullptr;   // hedit_unet_forward_shared: batch row -> distinct latent (null in a dry run)
   bool dry() const { return ar.dry; }
 };
@@ -488,8 +490,52 @@ int transformer_stem(Fwd& f, const Attn& a, const bf16_t* x, int H, int W, bf16_
                     ? pl->qk_src : nullptr;
     sp.kv_src = (pl && pl->kv_src && f.tblock >= pl->kv_first_block) ? pl->kv_src : nullptr;
     ++f.tblock;
+    // mask-guided MasaCtrl: class arrays of this token count, where the mutual attention applies (forward_checks has refused
+    // the combinations that cannot run: a hook, no kv_src, qk_src, a non-square latent)
+    const uint8_t *cls_q = nullptr, *cls_k = nullptr;
+    if (pl && pl->n_masa_rows > 0 && sp.kv_src && !pl->masa_auto) {
+      for (int r = 0; r < pl->n_masa_res && !cls_q; ++r)
+        if (pl->h_masa_tokens[r] == N) { cls_q = pl->h_masa_cls_q[r]; cls_k = pl->h_masa_cls_k[r]; }
+    } else if (pl && pl->n_masa_rows > 0 && sp.kv_src) {
+      // auto: the class array of this resolution from the maps collected so far in this pass; none yet: unmasked
+      const int layer = f.masa_layer++;
+      if (f.masa_count > 0 && N % 64 == 0 && N <= 4096) {
+        uint8_t* cls = (pl->h_masa_dump && layer < pl->n_masa_dump && pl->h_masa_dump[layer])
+                           ? pl->h_masa_dump[layer]
+                           : reinterpret_cast<uint8_t*>(pl->masa_ws) + (size_t)pl->masa_images * 2 * 256 * sizeof(float);
+        ProfScope ps(f, PK_SELF_ATTN, 0.0, 2048.0 * pl->masa_images + (double)B * N);
+        RUN(f, masa_auto_mask_launch(reinterpret_cast<const float*>(pl->masa_ws), f.masa_count, pl->masa_images, W, pl->masa_thres,
+                                     cls, f.st));
+        cls_q = cls_k = cls;
+      }
+    }
     if (f.h->hook) {
       TRY(hooked_attention(f, sp.q, sp.ldq, sp.k, sp.ldk, sp.vt, sp.ldvt, ao, C, N, N, N, heads, d, 0));
+    } else if (cls_q) {
+      ProfScope ps(f, PK_SELF_ATTN, 4.0 * B * (double)N * N * C, 8.0 * M * C);
+      // the rows that are not listed (the source rows) on the plain kernel, one launch per contiguous run with offset base
+      // pointers: it is batch-invariant, so they keep the bits of a pass without masks (and of the inversion's calls)
+      for (int r0 = 0; r0 < B;) {
+        auto listed = [&](int r) {
+          for (int i = 0; i < pl->n_masa_rows; ++i)
+            if (pl->h_masa_rows[i] == r) return true;
+          return false;
+        };
+        if (listed(r0)) { ++r0; continue; }
+        int r1 = r0 + 1;
+        while (r1 < B && !listed(r1)) ++r1;
+        SelfAttnParams run = sp;
+        run.q = sp.q + (size_t)r0 * N * sp.ldq; run.k = sp.k + (size_t)r0 * N * sp.ldk; run.vt = sp.vt + (size_t)r0 * N;
+        run.out = sp.out + (size_t)r0 * N * sp.ldo; run.B = r1 - r0; run.kv_src = nullptr;
+        RUN(f, self_attn_launch(run, f.st));
+        r0 = r1;
+      }
+      MaskedSelfAttnParams mp{};
+      mp.q = sp.q; mp.ldq = sp.ldq; mp.k = sp.k; mp.ldk = sp.ldk; mp.vt = sp.vt; mp.ldvt = sp.ldvt; mp.out = sp.out; mp.ldo = sp.ldo;
+      mp.B = B; mp.N = N; mp.heads = heads; mp.d = d;
+      mp.rows = pl->masa_rows; mp.n_rows = pl->n_masa_rows; mp.kv_src = sp.kv_src;
+      mp.cls_q = cls_q; mp.cls_k = cls_k;
+      RUN(f, masked_self_attn_launch(mp, f.st));
     } else {
       ProfScope ps(f, PK_SELF_ATTN, 4.0 * B * (double)N * N * C, 8.0 * M * C);      // q, k, v^T read, out written
       RUN(f, self_attn_launch(sp, f.st));
@@ -567,6 +613,21 @@ int transformer_rest(Fwd& f, const Attn& a, const bf16_t* x, bf16_t* t1, bf16_t*
     } else {
       ProfScope ps(f, PK_CROSS_ATTN, 4.0 * B * (double)N * HEDIT_MAXW * C, 4.0 * M * C + 4.0 * MC * C);
       RUN(f, cross_attn_launch(cp, f.st));
+    }
+    if (pl && pl->masa_auto && pl->n_masa_rows > 0 && N == 256 && !f.h->hook) {
+      // mask-guided MasaCtrl, auto variant: beside the fused kernel (which never forms them) the probabilities of the 2 n
+      // conditional rows -- the contiguous block from row 2 n -- are materialised and folded into the map accumulator
+      const int n = pl->masa_images;
+      float* acc = reinterpret_cast<float*>(pl->masa_ws);
+      float* probs = reinterpret_cast<float*>(reinterpret_cast<char*>(pl->masa_ws) + (size_t)n * 2 * 256 * sizeof(float) + (size_t)B * 4096);
+      AttnProbsParams ap{};
+      ap.q = q2 + (size_t)2 * n * N * C; ap.ldq = C; ap.k = k2 + (size_t)2 * n * HEDIT_CTXP * ldk2; ap.ldk = ldk2;
+      ap.probs = probs; ap.B = 2 * n; ap.N = N; ap.M = HEDIT_MAXW; ap.kstride = HEDIT_CTXP; ap.heads = heads; ap.d = d;
+      ProfScope ps(f, PK_CROSS_ATTN, 4.0 * n * (double)N * HEDIT_MAXW * C, 8.0 * n * heads * N * HEDIT_MAXW);
+      RUN(f, attn_probs_launch(ap, f.st));
+      RUN(f, masa_accumulate_launch(probs, heads, 2 * n, pl->masa_ref_tokens, pl->n_masa_ref, pl->masa_cur_tokens, pl->n_masa_cur,
+                                    acc, f.st));
+      ++f.masa_count;
     }
   }
   f.ar.free(q2);
@@ -718,6 +779,10 @@ int forward_impl(hedit_unet* h, const float* x, float t, const float* ctx, int B
     hedit_set_error("batch larger than " + std::to_string(h->iota_cap) + " rows");
     return HEDIT_ERR_ARG;
   }
+
+  // mask-guided MasaCtrl, auto variant: the map accumulator starts every pass at zero
+  if (!dry && plan && plan->mode > 0 && plan->masa_auto && plan->n_masa_rows > 0)
+    HIP_TRY(hipMemsetAsync(plan->masa_ws, 0, (size_t)plan->masa_images * 2 * 256 * sizeof(float), st));
 
   // ---- text context
   if (cx) {
@@ -1090,6 +1155,27 @@ static int forward_checks(hedit_unet* h, const float* x, const void* ctx, int B,
   const int lowest = (height / div) * (width / div);
   ARG_CHECK(lowest % 64 == 0, "lowest-resolution level must have a multiple of 64 tokens");
   TRY(store_require_loaded(h, "UNet"));
+  if (plan && plan->mode > 0 && plan->n_masa_rows > 0) {     // mask-guided MasaCtrl: refused by name before anything is launched
+    ARG_CHECK(!h->hook, "masa classes: the host-language attention hook cannot run class-matched attention");
+    ARG_CHECK(plan->kv_src, "masa classes need kv_src (whose keys, values and key classes a row reads)");
+    ARG_CHECK(!plan->qk_src, "masa classes exclude qk_src");
+    ARG_CHECK(height == width, "masa classes: non-square layer (the masks are interpolated to square layers)");
+    ARG_CHECK(plan->masa_rows && plan->h_masa_rows && plan->n_masa_rows <= B, "masa classes: the listed rows (device and host copy)");
+    for (int i = 0; i < plan->n_masa_rows; ++i)
+      ARG_CHECK(plan->h_masa_rows[i] >= 0 && plan->h_masa_rows[i] < B, "masa classes: listed rows must lie in [0, B)");
+    if (plan->masa_auto) {
+      const int n = plan->masa_images;
+      ARG_CHECK(n > 0 && B == 4 * n && plan->n_masa_rows == 2 * n, "masa auto: the batch must be 4 * masa_images rows, 2 * masa_images listed");
+      ARG_CHECK(plan->masa_ref_tokens && plan->n_masa_ref > 0 && plan->masa_cur_tokens && plan->n_masa_cur > 0, "masa auto: token lists");
+      ARG_CHECK(plan->masa_ws && reinterpret_cast<uintptr_t>(plan->masa_ws) % 16 == 0, "masa auto: masa_ws (16-byte aligned)");
+      const size_t need = (size_t)n * 2 * 256 * sizeof(float) + (size_t)B * 4096 + (size_t)n * 2 * h->cfg.heads * 256 * HEDIT_MAXW * sizeof(float);
+      ARG_CHECK(plan->masa_ws_bytes >= need, "masa auto: masa_ws is too small");
+    } else {
+      ARG_CHECK(plan->n_masa_res > 0 && plan->h_masa_cls_q && plan->h_masa_cls_k && plan->h_masa_tokens, "masa classes: class arrays");
+      for (int r = 0; r < plan->n_masa_res; ++r)
+        ARG_CHECK(plan->h_masa_cls_q[r] && plan->h_masa_cls_k[r] && plan->h_masa_tokens[r] > 0, "masa classes: a class array is missing");
+    }
+  }
   ARG_CHECK(!(h->hook && plan && plan->mode > 0), "an attention hook excludes the in-kernel edits of a plan (pass plan = NULL)");
   if (plan && plan->mode > 0) {
     ARG_CHECK(plan->n_pairs >= 0 && plan->n_pairs + plan->n_single > 0, "plan rows");

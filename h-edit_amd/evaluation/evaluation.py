@@ -51,18 +51,12 @@ NETWORK_METRICS = {"lpips": "torchmetrics LPIPS (SqueezeNet) weights", "structur
                    "clip_similarity_target_image_edit_part": "CLIP ViT-L/14 weights", "local_clip": "a local CLIP ViT-L/14 model (--clip_path) and a prompt-template file (--local_clip_templates)"}
 
 
-def mask_decode(encoded_mask, image_shape=(512, 512)):
-    """PIE-Bench run-length mask: pairs (start, length) over the flattened image; the one-pixel border is forced to 1
-    ("to avoid annotation errors in boundary", evaluation.py:9-25)."""
-    length = image_shape[0] * image_shape[1]
-    flat = np.zeros((length,))
-    enc = np.asarray(encoded_mask, dtype=np.int64).reshape(-1, 2) if len(encoded_mask) else np.zeros((0, 2), dtype=np.int64)
-    for start, run in enc:
-        flat[start:start + max(0, min(run, length - start))] = 1
-    m = flat.reshape(image_shape[0], image_shape[1])
-    m[0, :] = m[-1, :] = 1
-    m[:, 0] = m[:, -1] = 1
-    return m
+try:
+    from hedit.pie_mask import mask_decode  # noqa: F401  (the run-length mask decoding, shared with main_masactrl.py)
+except ImportError:      # run as a script: the `hedit` package lies one directory up
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from hedit.pie_mask import mask_decode  # noqa: F401
 
 
 def _pair(img_pred, img_gt, mask_pred, mask_gt, scale=255.0):

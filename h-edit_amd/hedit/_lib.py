@@ -59,7 +59,14 @@ class P2PPlan(C.Structure):
                 ("h_store", C.POINTER(C.c_void_p)), ("n_store", C.c_int),
                 ("kv_src", C.c_void_p), ("kv_first_block", C.c_int),
                 ("qk_first_block", C.c_int), ("qk_max_tokens", C.c_int), ("feat_src", C.c_void_p), ("feat_resblock", C.c_int),
-                ("h_store_self", C.POINTER(C.c_void_p)), ("n_store_self", C.c_int)]
+                ("h_store_self", C.POINTER(C.c_void_p)), ("n_store_self", C.c_int),
+                ("masa_rows", C.c_void_p), ("h_masa_rows", C.POINTER(C.c_int32)), ("n_masa_rows", C.c_int),
+                ("h_masa_cls_q", C.POINTER(C.c_void_p)), ("h_masa_cls_k", C.POINTER(C.c_void_p)),
+                ("h_masa_tokens", C.POINTER(C.c_int32)), ("n_masa_res", C.c_int),
+                ("masa_auto", C.c_int), ("masa_thres", C.c_float), ("masa_images", C.c_int),
+                ("masa_ref_tokens", C.c_void_p), ("n_masa_ref", C.c_int), ("masa_cur_tokens", C.c_void_p), ("n_masa_cur", C.c_int),
+                ("masa_ws", C.c_void_p), ("masa_ws_bytes", C.c_size_t),
+                ("h_masa_dump", C.POINTER(C.c_void_p)), ("n_masa_dump", C.c_int)]
 
 
 class StepCoef(C.Structure):
@@ -246,6 +253,12 @@ _SIGS = {    "hedit_last_error": (C.c_char_p, []),
     "hedit_k_geglu": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "hedit_k_self_attn": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hedit_k_masked_self_attn": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
+                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "hedit_k_masa_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                          C.c_void_p]),
+    "hedit_k_masa_auto_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
     "hedit_k_cross_attn": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p,
                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(P2PPlan), C.c_void_p,
                                      C.c_void_p]),

@@ -435,7 +435,7 @@ class UNet2DConditionModel(NativeOwner):
             if torch.is_grad_enabled() and (sample.requires_grad or ctx_grad):
                 if controller is not None:
                     what = "an attention editor" if controller is getattr(self, "_attention_editor", None) else "a registered controller"
-                    raise NotImplementedError(f"{what} is in the way: the input-gradient pass differentiates the plain network "
+                    raise NotImplementedError(f"{what} ({type(controller).__name__}) is in the way: the input-gradient pass differentiates the plain network "
                                               "only (pass cross_attention_kwargs={'use_controller': False, 'use_editor': False})")
                 return UNetOutput(sample=_EpsGrad.apply(sample, ctx, self, t))
         from .p2p.ptp_classes import runs_in_python

@@ -28,7 +28,8 @@
  *   hedit_attn_aggregate    replaces  aggregate_attention (p2p/ptp_classes.py:298-309): the mean over layers and heads of the
  *                                     averaged maps the attention viewers display
  *   hedit_p2p_plan          carries   the per-call edit rule of the registered controller / editor: Prompt-to-Prompt
- *                                     (ptp_classes.py:194-227), MasaCtrl (masactrl/masactrl.py:53-69: kv_src) and
+ *                                     (ptp_classes.py:194-227), MasaCtrl (masactrl/masactrl.py:53-69: kv_src; :71-148: the
+ *                                     mask-guided editor with given masks, masa_rows + class arrays) and
  *                                     Plug-and-Play (plug_n_play/pnp_utils.py:29-154: qk_first_block, feat_src)
  *   hedit_vae_encode/decode replaces  model.vae.encode(x).latent_dist.mode() / model.vae.decode(z).sample
  *                                     (main_p2p.py:159,263)
@@ -114,6 +115,52 @@ typedef struct {
    * on mode-2 passes (post-edit: inside the self window the target row's map is the source's).  NULL = off. */
   float* const* h_store_self;
   int n_store_self;
+  /* Mask-guided MasaCtrl (text-guided/masactrl/masactrl.py:71-148): where kv_src applies, the rows listed in masa_rows (the
+   * target rows) attend only to the keys of row kv_src[b] whose class equals the query's class; a query whose class has no key
+   * attends to all of them with equal weight (the reference's fp32 result: the mean of V).  masa_rows MUST list exactly the rows with
+   * kv_src[b] != b: the rows not listed (the source rows) run plain attention on their OWN keys and values on the unmasked
+   * kernel, launched on their contiguous runs, so they keep the bits of a pass without these fields -- a row with
+   * kv_src[b] != b that is left out would silently lose its mutual attention (kv_src is device memory: the executor cannot
+   * check it).  h_masa_rows is a HOST copy of masa_rows (the executor cuts the runs from it).
+   * Classes are bytes 0 / 1 per token, given per layer resolution: HOST arrays of n_masa_res device pointers,
+   * h_masa_cls_q[r] / h_masa_cls_k[r] = [B][h_masa_tokens[r]] (query classes read at row b, key classes at row kv_src[b]);
+   * h_masa_tokens is a HOST array of the token counts (multiples of 64 up to 4096).  A self-attention layer whose token count
+   * is not listed, or that lies outside the kv_first_block gate, runs as without these fields.  Needs kv_src and a square
+   * latent; excludes qk_src and an attention hook: each refused by name before anything is launched.  (The taped forward of
+   * hedit_unet_forward_keep / _vjp takes no plan at all.)  n_masa_rows = 0 = off. */
+  const int32_t* masa_rows;   /* [n_masa_rows] */
+  const int32_t* h_masa_rows; /* HOST [n_masa_rows] */
+  int n_masa_rows;
+  const uint8_t* const* h_masa_cls_q;
+  const uint8_t* const* h_masa_cls_k;
+  const int32_t* h_masa_tokens;
+  int n_masa_res;
+  /* The auto variant (masactrl.py:151-286): masa_auto = 1 derives the classes from the pass's own cross-attention maps
+   * instead of taking them from h_masa_cls_* (then NULL, n_masa_res = 0).  The batch is [x_orig|null]*n, [x_k|null]*n,
+   * [x_orig|src]*n, [x_k|tar]*n with n = masa_images, B = 4 n, masa_rows the 2 n target rows.  Every cross-attention layer
+   * with exactly 256 tokens adds the head mean of its probabilities -- the columns masa_ref_tokens summed on the n conditional
+   * source rows, masa_cur_tokens on the n conditional target rows (device arrays of token indices < 77) -- to an accumulator.
+   * Before a self-attention layer where kv_src applies, accumulator / layers-so-far is min-max normalised per image, taken
+   * nearest from 16 x 16 to the layer's resolution and thresholded >= masa_thres: the source map gives the key classes of
+   * image i's source rows, the target map the query classes of its target rows.  A constant map gives class 0 everywhere
+   * (the reference divides 0 by 0 there).  While the pass has collected no map, such a layer runs unmasked.  No host wait.
+   * masa_ws: caller-owned device memory, 16-byte aligned, of at least
+   *     2 n * 256 * 4  +  4 n * 4096  +  2 n * heads * 256 * 77 * 4   bytes
+   * (accumulator, class array, probabilities); the executor zeroes the accumulator at the start of the pass.
+   * h_masa_dump: optional HOST array of n_masa_dump device pointers, one per self-attention layer where kv_src applies, in
+   * call order: the class array [B][N] of that layer is written THERE (and read from there) instead of into masa_ws; a layer
+   * that ran unmasked leaves its buffer untouched. */
+  int masa_auto;
+  float masa_thres;
+  int masa_images;
+  const int32_t* masa_ref_tokens;
+  int n_masa_ref;
+  const int32_t* masa_cur_tokens;
+  int n_masa_cur;
+  void* masa_ws;
+  size_t masa_ws_bytes;
+  uint8_t* const* h_masa_dump;
+  int n_masa_dump;
 } hedit_p2p_plan;
 
 typedef struct {
@@ -487,6 +534,18 @@ int hedit_k_geglu(const void* x, void* y, int64_t rows, int inner, void* stream)
 int hedit_k_self_attn(const void* q, int ldq, const void* k, int ldk, const void* vt, int64_t ldvt,
                       void* out, int ldo, int B, int N, int heads, int d, const int32_t* qk_src, const int32_t* kv_src,
                       void* stream);
+/* class-matched mutual self-attention (hedit_p2p_plan.masa_rows): operands as hedit_k_self_attn; only the n_rows batch rows
+ * listed in `rows` are computed and written.  Row b reads k, v and the key classes cls_k [B][N] of row kv_src[b] and the query
+ * classes cls_q [B][N] of row b; bytes 0 / 1.  d in {32, 40, 64, 80, 160}, N % 64 == 0, 64 <= N <= 4096. */
+int hedit_k_masked_self_attn(const void* q, int ldq, const void* k, int ldk, const void* vt, int64_t ldvt, void* out, int ldo,
+                             int B, int N, int heads, int d, const int32_t* rows, int n_rows, const int32_t* kv_src,
+                             const uint8_t* cls_q, const uint8_t* cls_k, void* stream);
+/* the two small kernels of hedit_p2p_plan.masa_auto: acc [rows][256] += head mean of the summed token columns of
+ * probs [rows * heads][256][77] (the first rows / 2 rows sum the ref tokens, the others the cur tokens); and
+ * acc [2 n][256] / count -> cls [4 n][res * res] as described at masa_auto (res <= 64) */
+int hedit_k_masa_accumulate(const float* probs, int heads, int rows, const int32_t* ref_tokens, int n_ref,
+                            const int32_t* cur_tokens, int n_cur, float* acc, void* stream);
+int hedit_k_masa_auto_mask(const float* acc, int count, int n, int res, float thres, uint8_t* cls, void* stream);
 int hedit_k_cross_attn(const void* q, int ldq, const void* k, int ldk, const void* vt, int64_t ldvt,
                        void* out, int ldo, int B, int N, int heads, int d,
                        const hedit_p2p_plan* plan, float* store, void* stream);
